@@ -13,7 +13,13 @@ reference by its truncation-bound certificate + fp64 fix-up, tests/test_gpu_nuff
 photon x trial pairs the reference evaluates directly, and the NUFFT returns the same per-trial powers without
 evaluating every pair (``exact_path`` and ``cpu_baseline`` do evaluate every pair).
 
-Also reported:
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) sets up, settles and warms up, times the N steps and prints
+the result line: ``metric``, ``value``, ``unit``, ``ms_per_step``, the workload and the best trial. ``--dump-outputs
+DIR`` also writes what the last timed step returned (``best_power.npy``, ``best_index.npy``) and the per-trial powers
+of that same search (``powers.npy``) for an output-for-output comparison of two builds. Every other leg below runs
+only with ``--full``.
+
+Reported with ``--full``:
 * ``roofline``: the NUFFT's dominant kernel class, its algorithmic work per launch (crimp_last_nufft_work) over the
   mean launch time (hipEvents on the library's stream); every class under ``nufft.kernels``;
 * ``exact_path``: the default exact-integer path (k_search_exact) on the same inputs, ``--exact-steps`` steps, with
@@ -62,6 +68,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run every other leg: the NUFFT's per-kernel rooflines, the exact path, the CPU baselines, "
+                        "calcphase, the ToA legs, config 4 and config 2 (each can be skipped with its --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write DIR/best_power.npy and DIR/best_index.npy (what the last timed "
+                        "step returned) and DIR/powers.npy (the per-trial powers of that search, from one untimed "
+                        "repeat with the same inputs; a seeded sample when they exceed the size limit), float64")
     p.add_argument("--settle", type=float, default=0.3,
                    help="seconds of untimed steps before the warmup steps (GPU clocks back at steady state)")
     p.add_argument("--photons", type=int, default=10_000_000)
@@ -652,6 +665,22 @@ def pmc_clock():
         return None
 
 
+DUMP_MAX_VALUES = 6_000_000   # float64 values of powers.npy: 48 MB, under the 64 MB a dump may take in all
+
+
+def dump_outputs(d, best_pow, best_idx, powers):
+    """``--dump-outputs``: the timed step's return value and the per-trial powers behind it as float64 .npy files.
+    More than DUMP_MAX_VALUES powers are cut to a fixed sample: sorted indices drawn without replacement from
+    numpy's default_rng(0), the same for every run with the same grid."""
+    os.makedirs(d, exist_ok=True)
+    p = np.asarray(powers, dtype=np.float64)
+    if p.size > DUMP_MAX_VALUES:
+        p = p[np.sort(np.random.default_rng(0).choice(p.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(d, "best_power.npy"), np.array([best_pow], dtype=np.float64))
+    np.save(os.path.join(d, "best_index.npy"), np.array([best_idx], dtype=np.float64))
+    np.save(os.path.join(d, "powers.npy"), np.ascontiguousarray(p))
+
+
 def main():
     a = parse()
     import torch
@@ -699,7 +728,16 @@ def main():
         # ramp, not the steady state a search service runs at (20 steps after 3 warmups: 0.49 vs 0.43-0.44 ms per
         # step in a loop that had run for a while, profiles/r06/clock_settle.log)
         t_s = time.perf_counter()
-        while time.perf_counter() - t_s < a.settle:
+        while True:
+            go = time.perf_counter() - t_s < a.settle
+            if world > 1:
+                # a step holds a collective, so every rank runs the same number of them: the ranks' clocks started
+                # apart, and each deciding by its own left one rank waiting in a gather the others never entered
+                got = torch.tensor([1.0 if go else 0.0], dtype=torch.float64, device=dev)
+                dist.all_reduce(got, op=dist.ReduceOp.MIN)
+                go = got.item() > 0.0
+            if not go:
+                break
             step()
             torch.cuda.synchronize()
         for _ in range(warmup):
@@ -749,8 +787,15 @@ def main():
     el, kern_ms, nfix, (best_pow, best_idx), step_ms, path = timed_steps(
         prec, a.steps, a.warmup, flags=N.FLAG_TIME_KERNELS if a.precision == "exact" else 0)
     value = float(a.photons) * M * world * a.steps / el
+    if a.dump_outputs:
+        # the powers the timed step reduced to its best: the same search once more, untimed, every trial returned
+        # (a collective like the step's, so every rank calls it; rank 0 writes)
+        powers = sharded_search(t, f, a.nharm, 0, gather="all", precision=prec, t0=t0_h)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, best_pow, best_idx, powers.cpu().numpy())
+        del powers
     exact = None
-    if a.precision != "exact" and not a.no_exact:
+    if a.full and a.precision != "exact" and not a.no_exact:
         e_el, e_kms, e_nfix, e_best, _, _ = timed_steps("exact", a.exact_steps, 1, flags=N.FLAG_TIME_KERNELS)
         exact = exact_record(e_el, e_kms, e_nfix, a.exact_steps)
         exact["best_trial_index"], exact["best_power"] = e_best[1], float(e_best[0])
@@ -785,7 +830,7 @@ def main():
         if a.precision == "exact":
             ex = exact_record(el, kern_ms, nfix, a.steps)
             rec["roofline"] = dict(ex["roofline"], step_ms=step_ms)
-        else:
+        elif a.full:
             # the NUFFT's per-kernel rooflines from separately timed searches (hipEvent spans per kernel class)
             nu = nufft_leg(a, t, t_h, f, rank, M, max(3, a.steps))
             rec["roofline"] = dict(nu["roofline"], step_ms=step_ms,
@@ -799,21 +844,23 @@ def main():
             if exact is not None:
                 rec["exact_path"] = exact
                 rec["exact_path"]["same_best_trial"] = (exact["best_trial_index"] == best_idx)
-        if not a.no_cpu and world == 1:  # rank 0 at N=1 only
+        else:
+            rec["step_ms"] = step_ms   # hipEvents around the timed loop / steps (roofline.step_ms with --full)
+        if a.full and not a.no_cpu and world == 1:  # rank 0 at N=1 only
             rec["cpu_baseline"] = cpu_baseline(t_h, f0, df, a.nharm, a.cpu_seconds)
     del t, f
     torch.cuda.empty_cache()
-    if not a.no_calcphase and rank == 0:
+    if a.full and not a.no_calcphase and rank == 0:
         rec["calcphase"] = calcphase_leg(a, dev)
-    if not a.no_toa:
+    if a.full and not a.no_toa:
         toa = toa_leg(a, dev, world, rank)
         if rank == 0:
             rec.update(toa)
-    if not a.no_config4:
+    if a.full and not a.no_config4:
         c4 = config4_leg(a, dev, world, rank)
         if rank == 0:
             rec["config4"] = c4
-    if not a.no_config2 and rank == 0:
+    if a.full and not a.no_config2 and rank == 0:
         rec["config2"] = config2_leg(a)
     if rank == 0:
         print(json.dumps(rec), flush=True)

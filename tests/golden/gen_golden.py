@@ -119,9 +119,42 @@ def gti_fixture():
     print("gti rows", start.size)
 
 
+FITS_HEAD_ROWS = 256
+
+
+def fits_head_fixture():
+    """1e2259_ni1020600110_head.fits.gz (gzip, mtime 0): the bundled observation's FITS file cut to the first FITS_HEAD_ROWS rows of its
+    EVENTS table (all 14 columns, the mission's own headers; only the NAXIS2 card changes), every other HDU byte for
+    byte -- a real NICER event file small enough to commit, for the reader's test."""
+    buf = open(os.path.join(REF, "data", "1e2259_ni1020600110.fits"), "rb").read()
+    hstart = 2880   # the primary HDU has no data: the EVENTS header follows its one block
+    pos, cards = hstart, []
+    while True:
+        block = buf[pos:pos + 2880].decode("ascii")
+        pos += 2880
+        cards += [block[i:i + 80] for i in range(0, 2880, 80)]
+        if any(c[:8].strip() == "END" for c in cards[-36:]):
+            break
+    kv = {c[:8].strip(): c[10:].split("/")[0].strip() for c in cards if c[8:10] == "= "}
+    assert kv["EXTNAME"].strip("' ") == "EVENTS" and int(kv.get("PCOUNT", 0)) == 0
+    w, nrow = int(kv["NAXIS1"]), int(kv["NAXIS2"])
+    i = next(j for j, c in enumerate(cards) if c[:8].strip() == "NAXIS2")
+    cards[i] = cards[i].replace("%20d" % nrow, "%20d" % FITS_HEAD_ROWS, 1)
+    assert len(cards[i]) == 80 and int(cards[i][10:30]) == FITS_HEAD_ROWS
+    data = buf[pos:pos + w * FITS_HEAD_ROWS]
+    data += b"\0" * (((len(data) + 2879) // 2880) * 2880 - len(data))
+    rest = buf[pos + ((w * nrow + 2879) // 2880) * 2880:]
+    import gzip
+    with open(os.path.join(HERE, "1e2259_ni1020600110_head.fits.gz"), "wb") as raw:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0) as fh:
+            fh.write(buf[:hstart] + "".join(cards).encode("ascii") + data + rest)
+    print("fits head rows", FITS_HEAD_ROWS, "of", nrow)
+
+
 def main():
     out = {}
     gti_fixture()
+    fits_head_fixture()
     # ---------------------------------------------------------------- data files
     for fn in ("1e2259.par", "1e2259_template.txt", "timIntToAs_1e2259.txt", "ToAs_2259.txt", "ToAs_2259.tim"):
         shutil.copyfile(os.path.join(REF, "data", fn), os.path.join(HERE, fn))

@@ -164,17 +164,25 @@ def test_eventfile_roundtrip_and_toa_mid(tmp_path):
         assert str(mid) == str(ref[ref["ToA"] == ii]["ToA_mid"].iloc[0])
 
 
-def test_eventfile_reads_bundled_fits_if_present():
+def test_eventfile_reads_bundled_fits_if_present(tmp_path):
+    """The mission's own file, as bundled with the reference: tests/golden/1e2259_ni1020600110_head.fits.gz is that
+    file (gzipped) with its EVENTS table (all 14 columns, its own headers) cut to the first 256 rows and every other
+    HDU byte for byte (gen_golden.fits_head_fixture)."""
+    import gzip
     from crimp_amd.eventfile import EvtFileOps
-    p = "/root/reference/data/1e2259_ni1020600110.fits"
-    if not os.path.exists(p):
-        pytest.skip("reference data not mounted")
-    ev = gold("events_1e2259.npz")
+    ev, g = gold("events_1e2259.npz"), gold("gti_1e2259.npz")
+    p = str(tmp_path / "head.fits")
+    with gzip.open(gpath("1e2259_ni1020600110_head.fits.gz"), "rb") as src, open(p, "wb") as dst:
+        dst.write(src.read())
     ef = EvtFileOps(p)
     df = ef.build_time_energy_df().time_energy_df
-    assert np.array_equal(df["TIME"].to_numpy(), ev["TIME"] / 86400 + (int(ev["MJDREFI"]) + float(ev["MJDREFF"])))
+    mjdref = int(ev["MJDREFI"]) + float(ev["MJDREFF"])
+    assert len(df) == 256
+    assert np.array_equal(df["TIME"].to_numpy(), ev["TIME"][:256] / 86400 + mjdref)
+    assert np.array_equal(df["PI"].to_numpy(), ev["PI"][:256] * 0.01)
     kw, gti = ef.readGTI()
     assert kw["TELESCOPE"] == "NICER" and gti.shape[1] == 2
+    assert np.array_equal(gti, np.vstack((g["START"], g["STOP"])).T / 86400 + mjdref)
 
 
 def test_binphases_host_matches_reference():

@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 step() { echo "[$1] rc=$2"; [ "$2" -ne 0 ] && exit "$2"; return 0; }
 timeout -k 10 ${BENCH_TIMEOUT:-420} rocprofv3 --kernel-trace --stats -d "$OUT/bench_trace" -o bench --output-format csv \
-    -- python3 bench.py ${BENCH_ARGS:-} > "$OUT/bench_traced.log" 2>&1
+    -- python3 bench.py --full ${BENCH_ARGS:-} > "$OUT/bench_traced.log" 2>&1
 step bench-trace $?
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $c --kernel-trace -d "$OUT/pmc_$c" -o pmc --output-format csv \
