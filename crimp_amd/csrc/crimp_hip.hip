@@ -549,9 +549,6 @@ __device__ __forceinline__ void photon_sincos(int model, double xv, double& s1, 
 // the library sincospi / sincos): r = x in turns (x / 2 pi for radians), k = rint(4096 r), delta = 2 pi (r - k / 4096)
 // (the subtraction is exact), |delta| <= pi / 4096, cos/sin(delta) by their Taylor series to delta^4 / delta^5
 // (truncation < 3e-22), rotated by the table entry: ~2 ulp, against ~30 fp64 operations of the library call.
-#ifndef CRIMP_FIT_GENERIC
-#define CRIMP_FIT_GENERIC 0
-#endif
 #ifndef CRIMP_FIT_TABLE
 #define CRIMP_FIT_TABLE 1
 #endif
@@ -581,17 +578,10 @@ __device__ __forceinline__ void photon_sincos_tab(int model, const double2* __re
 // rounded division; measured equal to 1/v on 2^24 values, one step alone 11 ulps, v_rcp_f64 alone 2^-24.6:
 // profiles/r06/mb_rcp.txt). The fit kernels and k_toa_points use the same, so the device-driven and the
 // host-driven fits sum identical terms.
-#ifndef CRIMP_FIT_EXACT_DIV
-#define CRIMP_FIT_EXACT_DIV 0
-#endif
 __device__ __forceinline__ double lk_rcp(double v) {
-#if CRIMP_FIT_EXACT_DIV
-    return 1.0 / v;
-#else
     double r = __builtin_amdgcn_rcp(v);
     r = fma(fma(-v, r, 1.0), r, r);
     return fma(fma(-v, r, 1.0), r, r);
-#endif
 }
 
 // h = model - norm at one photon and its first two phShift derivatives h1, h2 (templatemodels.py:64-82,
@@ -1038,14 +1028,11 @@ __global__ __launch_bounds__(kGridBlock) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
 // CRIMP_GM_PREF: each thread loads its photon of the next tile right after building the current one, so the global
 // load's latency passes under the current tile's chunks instead of stalling every wave of the block at the build.
-// (1.85 -> 1.82 ms per 1250 config-5 grids, profiles/r04/ab_toa_pipe.log.) CRIMP_GM_PIPE=1 (A/B build): a wave
-// issues the next chunk's MFMAs before the VALU work on the current chunk's results; it measured slower (1.88 ms):
-// the five resident waves per SIMD already overlap one wave's MFMAs with another's VALU work.
+// (1.85 -> 1.82 ms per 1250 config-5 grids, profiles/r04/ab_toa_pipe.log.) Measured, rejected and removed: a wave
+// issuing the next chunk's MFMAs before the VALU work on the current chunk's results (1.88 ms, the same log): the
+// five resident waves per SIMD already overlap one wave's MFMAs with another's VALU work.
 #ifndef CRIMP_GM_PREF
 #define CRIMP_GM_PREF 1
-#endif
-#ifndef CRIMP_GM_PIPE
-#define CRIMP_GM_PIPE 0
 #endif
 constexpr int kGmTile = CRIMP_GM_TILE, kGmPad = CRIMP_GM_PAD;
 static_assert(kGmTile == 128 || kGmTile == 256, "k_toa_grid_mf: one or two of the block's 256 threads per photon");
@@ -1246,18 +1233,7 @@ __global__ __launch_bounds__(256) void k_toa_grid_mf(const double* __restrict__ 
 #pragma unroll
             for (int a = 0; a < NN; ++a) acc[a] += (double)pa[a / 2][a % 2];
         };
-        if constexpr (CRIMP_GM_PIPE) {  // ping-pong: chunk q + 1's MFMAs issue before chunk q's VALU work
-            f32x16 ha = chunk_mfma(0), hb = {};
-            for (int q0 = 0; q0 < cnt; q0 += 64) {
-                if (q0 + 32 < cnt) hb = chunk_mfma(q0 + 32);
-                chunk_valu(ha, q0);
-                if (q0 + 32 >= cnt) break;
-                if (q0 + 64 < cnt) ha = chunk_mfma(q0 + 64);
-                chunk_valu(hb, q0 + 32);
-            }
-        } else {
-            for (int q0 = 0; q0 < cnt; q0 += 32) chunk_valu(chunk_mfma(q0), q0);
-        }
+        for (int q0 = 0; q0 < cnt; q0 += 32) chunk_valu(chunk_mfma(q0), q0);
     }
     // the column's two lane halves: half 0 + half 1
 #pragma unroll
@@ -2913,10 +2889,7 @@ static int toa_fit_impl(const double* x, const int64_t* offsets, int64_t nint, c
 #define CRIMP_LF(MD, KK) k_toa_fit<MD, KK><<<(unsigned)fn, kFitBlock, 0, st>>>(dx, doff + f0, dT, de + f0, dstart + 2 * f0, \
                                                                              C, dout + 8 * f0, hcache)
             if (T.model == CRIMP_MODEL_FOURIER) {
-#if CRIMP_FIT_GENERIC  // A/B build: the template size read at run time
-                CRIMP_LF(CRIMP_MODEL_FOURIER, 0);
-#else
-                switch (T.K) {
+                switch (T.K) {  // the template size at compile time (0: read at run time)
                     case 1: CRIMP_LF(CRIMP_MODEL_FOURIER, 1); break;
                     case 2: CRIMP_LF(CRIMP_MODEL_FOURIER, 2); break;
                     case 3: CRIMP_LF(CRIMP_MODEL_FOURIER, 3); break;
@@ -2927,7 +2900,6 @@ static int toa_fit_impl(const double* x, const int64_t* offsets, int64_t nint, c
                     case 8: CRIMP_LF(CRIMP_MODEL_FOURIER, 8); break;
                     default: CRIMP_LF(CRIMP_MODEL_FOURIER, 0); break;
                 }
-#endif
             } else if (T.model == CRIMP_MODEL_CAUCHY) {
                 CRIMP_LF(CRIMP_MODEL_CAUCHY, 0);
             } else {
@@ -2935,52 +2907,25 @@ static int toa_fit_impl(const double* x, const int64_t* offsets, int64_t nint, c
             }
 #undef CRIMP_LF
         };
-        // Brute grid, then fits, in sequence on the caller's stream. CRIMP_TOA_OVERLAP=1 (A/B build switch, read per
-        // call) runs the intervals in two halves on two streams instead, the second half's grid beside the first half's
-        // fits (every interval's fit is independent of its batch, so the records are those of the sequential order):
-        // measured slower on config 5 (6.1 vs 5.7 ms per 1250 intervals, profiles/r04/toa_breakdown.log) -- each half's
-        // fit runs 1.2 rounds of the resident workgroups and its grid half as many blocks, so the tails grow, not shrink
+        // Brute grid, then fits, in sequence on the caller's stream. Measured, rejected and removed: the intervals in two
+        // halves on two streams, the second half's grid beside the first half's fits (config 5: 6.1 vs 5.7 ms per 1250
+        // intervals, profiles/r04/toa_breakdown.log) -- each half's fit runs 1.2 rounds of the resident workgroups and its
+        // grid half as many blocks, so the tails grow, not shrink
         auto all = [&](int md) -> int {
             const bool timed = flags & CRIMP_FLAG_TIME_KERNELS;
-            const bool overlap = run_brute && !timed && nint >= 2 * 512 && getenv("CRIMP_TOA_OVERLAP") != nullptr;
-            if (!overlap) {
-                KernelTimer kg(s, timed);  // brute grid: k_toa_grid(_mf) + k_toa_grid_best
-                kg.start();
-                if (run_brute) {
-                    const int r2 = run_brute(md, s, 0, nint);
-                    if (r2) return r2;
-                }
-                if (run_brute) kg.stop();
-                KernelTimer kf(s, timed);  // the fit kernel
-                kf.start();
-                fit(s, 0, nint);
-                HIPCHK(hipGetLastError());
-                kf.stop();
-                return CRIMP_OK;
+            KernelTimer kg(s, timed);  // brute grid: k_toa_grid(_mf) + k_toa_grid_best
+            kg.start();
+            if (run_brute) {
+                const int r2 = run_brute(md, s, 0, nint);
+                if (r2) return r2;
             }
-            hipStream_t s1 = aux_stream();
-            if (!s1) return set_err(CRIMP_ERR_HIP, "cannot create the auxiliary stream");
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            HIPCHK(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-            const int64_t h = nint / 2;
-            int r2 = run_brute(md, s, 0, h);
-            if (!r2) {
-                HIPCHK(hipEventRecord(e0, s));
-                fit(s, 0, h);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipStreamWaitEvent(s1, e0, 0));
-                r2 = run_brute(md, s1, h, nint - h);
-            }
-            if (!r2) {
-                fit(s1, h, nint - h);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(e1, s1));
-                HIPCHK(hipStreamWaitEvent(s, e1, 0));
-            }
-            (void)hipEventDestroy(e0);  // destruction waits for nothing; the events complete in stream order
-            (void)hipEventDestroy(e1);
-            return r2;
+            if (run_brute) kg.stop();
+            KernelTimer kf(s, timed);  // the fit kernel
+            kf.start();
+            fit(s, 0, nint);
+            HIPCHK(hipGetLastError());
+            kf.stop();
+            return CRIMP_OK;
         };
         ht.mark("setup");
         if (hist_pending) {  // redChi2's histogram on the auxiliary stream, beside the grid and the fits

@@ -25,11 +25,14 @@
 //                 tile to the cell's slot: slot(chunk c, cell G) = G - G_min + c is unique per (c, G).
 //   k_nu_merge    slots -> W[batch][g]: every wrapped cell g sums its unwrapped cells G = g (mod n) and, per G, the
 //                 chunks that hold it, in chunk order (deterministic), transposed to batch-major rows.
-//   k_nu_fft_cols, k_nu_fft_rows   four-step FFT (n = n1 n2, Stockham autosort stages of radix 16/8/4/2 in LDS,
-//                 positive exponent); a single row pass for n <= 4096.
-//   k_nu_combine  the moments' Bessel-weighted sum at every trial -> (C_k, S_k) (fused into the row pass by
-//                 default: k_nu_rows_combine8 / k_nu_fft_rows_combine).
-//   k_nu_finalize Z^2 / H in the reference's formula order and the certificate (fix-up list, as the exact path).
+//   k_nu_cellstart, k_nu_gather   the spread of grids of <= kNuGatherRows rows: one lane per wrapped cell sums its
+//                 photons' moments in registers, straight into W (no slots, no merge).
+//   k_nu_fft_cols (k_nu_cols256, k_nu_cols512 for n1 = 256, 512)   pass 1 of the four-step FFT (n = n1 n2, n2 = 4096;
+//                 Stockham autosort stages in LDS, positive exponent); n <= 4096 has no pass 1.
+//   k_nu_fft_rows_combine (k_nu_rows_iw for n2 = 4096, k_nu_rows_combine8<11> for n = 2048)   pass 2, the rows, with
+//                 the moments' Bessel-weighted sum at every trial -> (C_k, S_k) kept in registers across the moments.
+//   k_nu_finalize Z^2 / H in the reference's formula order and the certificate (fix-up list, as the exact path); the
+//                 last harmonic's k_nu_rows_iw / k_nu_rows_combine8 launch does it in its epilogue instead.
 #pragma once
 
 typedef double nu_f64x4 __attribute__((ext_vector_type(4)));
@@ -376,8 +379,8 @@ struct NuCellArgs {
     int64_t gmin[kNuCellK], span[kNuCellK], off[kNuCellK];
 };
 // The cell gather's plans take the photon order from here too (no k_nu_sorted pass): a pair out of order sets *bad
-// (the search then takes the default path) and the writes stay inside the tables, which the host zeroes first, so
-// every entry is a photon index in [0, n] whatever the order.
+// (the search then takes the default path) and the writes stay inside the tables (every cell is clamped to its
+// harmonic's range). The tables are not zeroed: on unsorted photons the gathers read none of them (*bad).
 // Photon pairs (one 16-byte load when t is 16-byte aligned, VEC), kNuCellU pairs per thread and sweep with their
 // loads issued together, over at most 2048 blocks: the predecessor of a pair's first photon is the previous lane's
 // second one (a shuffle; lane 0 loads it). One 8-byte load per iteration ran at ~2 TB/s, and one pair per thread
@@ -390,7 +393,7 @@ constexpr int kNuCellU = 4;
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_nu_cellstart(const double* __restrict__ tt, double t0, int64_t n, double s1,
                                                       int k0, int nk, NuCellArgs a, int64_t* __restrict__ start,
-                                                      int* __restrict__ bad, int mode) {
+                                                      int* __restrict__ bad) {
     if (*bad) return;  // a cached plan that no longer holds (k_ap_final): no table is written
     const int64_t npair = (n + 1) / 2, stride = (int64_t)gridDim.x * blockDim.x;
     const int lane = threadIdx.x & 63;
@@ -422,10 +425,9 @@ __global__ __launch_bounds__(256) void k_nu_cellstart(const double* __restrict__
             const bool v0 = i0 < n, v1 = i0 + 1 < n;
             const int ooo = (v0 && !(dp0 <= d0)) || (v1 && !(d0 <= d1));
             b |= ooo;
-            if (mode == 1) continue;  // A/B probe: loads and order check only (the search is then discarded)
             // a wave that holds a pair out of order writes nothing for its photons (a vote, no block barrier: the
-            // barrier cost a quarter of the pass; mode 2, A/B: the lanes' own pairs only)
-            if (mode == 2 ? ooo : __any(ooo)) continue;
+            // barrier cost a quarter of the pass)
+            if (__any(ooo)) continue;
             // per harmonic the cells of the predecessor and of the pair's two photons, each formed once (the second
             // photon's range starts at the first one's cell); cells fit 32 bits (nu_plan checks |G| + n < 2^31): one
             // v_cvt_i32_f64 each, and 32-bit bounds
@@ -453,7 +455,6 @@ __global__ __launch_bounds__(256) void k_nu_cellstart(const double* __restrict__
         }
     }
     if (__any(b) && lane == 0) atomicOr(bad, 1);
-    if (mode == 1 && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(bad, 1);  // the probe's tables are not written
 }
 
 // L lanes per wrapped cell g sum, over its unwrapped cells G = g (mod n) and their photons in time order (lane s
@@ -957,7 +958,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     }
 }
 
-// k_nu_fft_cols for n1 = 512 (n = 512 n2; CRIMP_NUFFT_ROW2048=1): groups of 8 columns (NC = 1: 128 VGPRs, two blocks
+// k_nu_fft_cols for n1 = 512 (n = 2^21): groups of 8 columns (NC = 1: 128 VGPRs, two blocks
 // per CU; 16 columns at 248 VGPRs and one block measured 10 % slower), 512 threads (column cc = t & 7, j = t >> 3),
 // three radix-8 Stockham stages over rows j + 64 q (8 elements per thread and column: rows as loaded, stage 3's outputs
 // k1 = j + 64 q stored from registers), two exchanges through a [512 rows][8 columns] tile (conflict-free without a
@@ -1065,24 +1066,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     }
 }
 
-// pass 2 (or the only pass): DFT of 2^lr contiguous rows of length 2^ll each, in place
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_nu_fft_rows(double2* __restrict__ X, int ll, int lr, int lnfft) {
-    extern __shared__ double2 nu_s[];
-    __shared__ NuTile tw;
-    const int lt = lnfft < 12 ? lnfft : 12;
-    nu_tile_init(&tw, lt);
-    const int L = 1 << ll;
-    double2* x = X + ((int64_t)blockIdx.x << (ll + lr));
-    for (int e = threadIdx.x; e < (L << lr); e += 256) nu_s[e] = x[e];
-    __syncthreads();
-    nu_fft_lds(nu_s, ll, lr, 1, L, &tw, lt);
-    for (int e = threadIdx.x; e < (L << lr); e += 256) x[e] = nu_s[e];
-}
-
-// Pass 2 of the FFT fused with the combine: block (k1, r) transforms row k1 (length 2^ll = n2) of every moment p of
-// trial-grid row r, from p = P-1 down to 0, and keeps the Horner sum A = B_p + (z / (p+1)) A of its 2^ll positions in
-// registers (z = 2 pi i jc / n), so the moments' transforms are read once and never written back; the trials' (C_k,
-// S_k) go to CS as k_nu_combine writes them. X[beta][pos], beta = p * nrow + r, pos = k1 n2 + k2 holds J = k1 + n1 k2.
+// Pass 2 of the FFT (or the only pass) with the moments' sum: block (k1, r) transforms row k1 (length 2^ll = n2) of
+// every moment p of trial-grid row r, from p = P-1 down to 0, and keeps the Bessel-weighted sum
+// A = sum_p eps_p i^p J_p(z) B_p (nu_bes; z = pi jc / n) of its 2^ll positions in registers, so the moments' transforms
+// are read once and never written back; the trials' (C_k, S_k) go to CS[t], t the trial's index in the batch.
+// X[beta][pos], beta = p * nrow + r, pos = k1 n2 + k2 holds J = k1 + n1 k2 (ln1 = 0: natural order), J = jc mod n.
 constexpr int kNuFusedPer = kNuTile / 256;  // positions per thread
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k_nu_fft_rows_combine(const double2* __restrict__ X, int ll, int lnfft, int P,
                                                              int nrow, int64_t nf, int64_t jhi, int64_t h,
@@ -1128,7 +1116,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k
                 const double2 v = nu_s[b];
                 const int64_t J = k1 + ((int64_t)b << ln1);
                 const int64_t jc = J <= jhi ? J : J - nfft;  // positions between the two ends hold no trial
-                // k_nu_combine's arithmetic exactly: eps_p i^p J_p(z), z/2 = (pi/2) jc / n (nu_bes_w)
+                // eps_p i^p J_p(z), z/2 = (pi/2) jc / n (nu_bes_w)
                 acc[q] = nu_bes_acc(acc[q], nu_bes_w(bs[q], p, nu_zh(jc, lnfft)), v, p);
             }
         }
@@ -1151,103 +1139,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k
     }
 }
 
-// k_nu_fft_rows_combine for n2 = 4096 (the four-step FFT's rows; three radix-16 stages): the same arithmetic as
-// nu_fft_lds (the same stages, twiddles and butterflies, so bit-identical powers) with stage 1 on the row as loaded
-// into registers (thread t holds elements t + 256 r) and stage 3's outputs -- positions t + 256 r -- kept in registers
-// for the Horner sum: the tile is written and read twice per moment instead of four times. Two 64 KB tiles (stage 1
-// -> A, stage 2 -> B) leave two barriers per moment; element i of a tile is stored at i ^ ((i >> 4) & 15), which
-// spreads stage 1's stride-16 writes over all banks. The next moment's row loads are issued before the transform.
-__device__ __forceinline__ int nu_sw(int i) { return i ^ ((i >> 4) & 15); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k_nu_rows4096_combine(
-    const double2* __restrict__ X, int lnfft, int P, int nrow, int64_t nf, int64_t jhi, int64_t h, int64_t tbase,
-    int64_t nbt, const double* __restrict__ bc, double2* __restrict__ CS) {
-    extern __shared__ double2 nu_s[];  // [2][4096]
-    __shared__ NuTile tw;
-    nu_tile_init(&tw, 12);
-    double2* A = nu_s;
-    double2* B = nu_s + 4096;
-    const int64_t nfft = int64_t(1) << lnfft;
-    const int ln1 = lnfft - 12;
-    const int64_t k1 = blockIdx.x;
-    const int r = blockIdx.y;
-    const int t = threadIdx.x;
-    const double2* xr = X + (int64_t)r * nfft + (k1 << 12);
-    const int64_t pstride = (int64_t)nrow * nfft;
-    double2 acc[16], nx[16], v[16];
-    NuBes bs[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        acc[q] = make_double2(0.0, 0.0);
-        const int64_t J = k1 + ((int64_t)(t + 256 * q) << ln1);
-        bs[q] = nu_bes_start(bc, P, nu_zh(J <= jhi ? J : J - nfft, lnfft));
-        nx[q] = xr[(int64_t)(P - 1) * pstride + t + 256 * q];
-    }
-    // twiddle indices of this thread's butterflies (units of w_4096): stage 2 w_256^{t & 15}, stage 3 w_4096^t
-    const int m2 = (t & 15) << 4, m3 = t;
-    const int z0 = ((t >> 4) << 8) + (t & 15);  // stage 2's output base
-    __syncthreads();                            // tw
-    for (int p = P - 1; p >= 0; --p) {
-        const int64_t pn = (int64_t)(p > 0 ? p - 1 : 0) * pstride;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            v[q] = nx[q];
-            nx[q] = xr[pn + t + 256 * q];
-        }
-        nu_dft16(v);  // stage 1 (Ns = 1: no twiddles)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) A[nu_sw(16 * t + q)] = v[q];
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = A[nu_sw(t + 256 * q)];
-        nu_twiddle<16>(nu_tw_tile(&tw, m2), v);
-        nu_dft16(v);  // stage 2 (Ns = 16)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) B[nu_sw(z0 + 16 * q)] = v[q];
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = B[nu_sw(t + 256 * q)];
-        nu_twiddle<16>(nu_tw_tile(&tw, m3), v);
-        nu_dft16(v);  // stage 3 (Ns = 256): output position t + 256 q
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int64_t J = k1 + ((int64_t)(t + 256 * q) << ln1);
-            const int64_t jc = J <= jhi ? J : J - nfft;
-            acc[q] = nu_bes_acc(acc[q], nu_bes_w(bs[q], p, nu_zh(jc, lnfft)), v[q], p);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int64_t J = k1 + ((int64_t)(t + 256 * q) << ln1);
-        int64_t jc;
-        if (J <= jhi)
-            jc = J;
-        else if (J >= nfft - h)
-            jc = J - nfft;
-        else
-            continue;
-        const int64_t tt = tbase + r * nf + jc;
-        if (tt >= 0 && tt < nbt) CS[tt] = acc[q];
-    }
-}
-
-// k_nu_rows4096_combine with 512 threads and four radix-8 stages (8 elements per thread): two waves per SIMD from
-// one block per CU (the radix-16 form holds 16 elements per thread and runs one). Stage 1 on the loaded row, stage 4's
-// outputs (positions t + 512 r) in registers for the moment sum, stages 2-3 through two padded 72 KB tiles whose
-// roles alternate between moments (three barriers per moment). The transform's arithmetic differs from the radix-16
-// form's in rounding only. Measured (profiles/r06/ab_p2_probes.log, config 3): without its loads the pass takes 0.90
+// The radix-8 row passes (k_nu_rows_combine8<11>: rows of 2048; k_nu_rows_iw: rows of 4096): k_nu_fft_rows_combine's
+// sum with 8 elements per thread, so that two waves per SIMD run. Stage 1 on the row as loaded, the last stage's outputs
+// in registers for the moment sum, the stages between through two LDS tiles whose roles alternate between moments. The
+// transform's arithmetic differs from nu_fft_lds's radix-16 stages in rounding only. Measured on rows of 4096
+// (profiles/r06/ab_p2_probes.log, config 3): without its loads the pass takes 0.90
 // of its time, without its LDS exchanges 0.85, without the transform's arithmetic 0.81, without both 0.69 -- the
 // loads, exchanges and arithmetic of one block per CU overlap little; 30 % fewer VALU instructions (below) or a second
 // moment's loads in flight moved it by 1-2 %, rows of 2048 with two blocks per CU by 9 % (pass 1 then needs 512-row
 // columns), an L2 touch of the rows two moments ahead cost 12 % (profiles/r06/ab_p2_l2prefetch_rejected.log).
-// Moment chunks: the launch transforms moments plo .. P-1 (X holds their planes only, beta = (p - plo) nrow + r) and,
-// with accum, adds its partial sum to the CS an earlier chunk (moments above P) wrote -- the sum over moments is
-// linear, and each chunk starts the Bessel recurrence at its own top (nu_bes_start(P)).
+// Measured, rejected and removed: a 256-thread radix-16 form with 16 elements per thread, one wave per SIMD (0.190 vs
+// 0.178 ms per config-3 search, profiles/r05/ab_r8_ilp.log); the moments in chunks, pass 1 and pass 2 of a chunk in
+// turn with the partial sums carried through CS (slower at every chunk size, profiles/r06/ab_pchunk.log); n = 2^20 as
+// 512 x 2048 (pass 2 0.160 vs 0.180 ms, pass 1 0.138 vs 0.115 ms per config-3 search: a wash,
+// profiles/r06/ab_rows2048_cols512.log); pass 2 and the moment sum as two kernels.
+// Arguments plo and accum are what is left of the moment chunks: a launch transforms moments plo .. P-1 (X holds their
+// planes only, beta = (p - plo) nrow + r) and, with accum, starts from the sum CS holds instead of zero. The host
+// always passes 0, 0. They stay because the register allocation hangs on them: with both folded away (accumulator
+// from zero, unconditional prefetch of the next row, no rotation at the end) the compiler gives k_nu_rows_iw 256 VGPRs
+// and spills 17 (with them: 252, none) and k_nu_rows_combine8<11> 236 (221).
 // The last harmonic's launch may finalize (NuFinal.on): its sums stay in registers and each trial's power and
 // certificate are formed there from the earlier harmonics' CS (nu_power), the fix-up list appended, and the block's
 // best trial (np.argmax semantics) written to best_part for k_best_final -- no CS write, no finalize launch, no
 // reduction pass over the powers.
 struct NuFinal {
-    int on, m, stat, Pc;           // Pc: the plan's moments (the certificate), P of the launch may be a chunk's top
+    int on, m, stat, Pc;           // Pc: the plan's moments P (the certificate's truncation bound)
     double nph, invfact, rel;
     int64_t tb0;                   // out index of the batch's trial 0
     double* out;
@@ -1334,16 +1250,17 @@ struct NuRot {
 };
 // dynamic LDS of k_nu_rows_combine8<LN2>: two padded tiles
 constexpr size_t nu_rows_lds(int ln2) { return 2 * ((size_t(1) << ln2) + (size_t(1) << (ln2 - 3))) * sizeof(double2); }
-// LN2 = 12: rows of 4096, 512 threads, four radix-8 stages (Ns = 1, 8, 64, 512). LN2 = 11: rows of 2048 (n = 2^20:
-// columns of 512, k_nu_cols512), 256 threads, one radix-4 stage (butterflies t and t + 1024 on v[0, 2, 4, 6] and
-// v[1, 3, 5, 7]) then three radix-8 (Ns = 4, 32, 256): half the LDS and threads, two blocks per CU.
+// LN2 = 11, the one instantiation: rows of 2048 (n = 2048, a single pass), 256 threads, one radix-4 stage (butterflies
+// t and t + 1024 on v[0, 2, 4, 6] and v[1, 3, 5, 7]) then three radix-8 (Ns = 4, 32, 256), three block-wide exchanges
+// per moment. Rows of 4096 take k_nu_rows_iw; this kernel's 512-thread form for them (four radix-8 stages) was
+// measured slower (0.180 vs 0.171 ms per config-3 search, profiles/r06/ab_p2_iw.log) and removed.
 template <int LN2>
 __global__ __launch_bounds__(1 << (LN2 - 3)) __attribute__((amdgpu_waves_per_eu(2))) void k_nu_rows_combine8(
     const double2* X, int lnfft, int P, int plo, int accum, int nrow, int64_t nf, int64_t jhi, int64_t h,
     int64_t tbase, int64_t nbt, const double* __restrict__ bc, double2* __restrict__ CS, const NuFinal F) {
     constexpr int N = 1 << LN2, TPB = N / 8, NT = N + N / 8;
-    constexpr int Ns2 = LN2 == 12 ? 8 : 4, Ns3 = 8 * Ns2;
-    static_assert(LN2 == 11 || LN2 == 12, "rows of 2048 or 4096");
+    constexpr int Ns2 = 4, Ns3 = 8 * Ns2;
+    static_assert(LN2 == 11, "rows of 2048");
     extern __shared__ double2 nu_s[];  // [2][NT]
     __shared__ NuTile tw;
     nu_tile_init(&tw, LN2);
@@ -1363,7 +1280,7 @@ __global__ __launch_bounds__(1 << (LN2 - 3)) __attribute__((amdgpu_waves_per_eu(
     };
     double2 acc[8], xa[8], xb[8];
     NuRot bs[8];
-    // the frame at the top moment: T_P = i^-P S_P (S_P: an earlier chunk's sum at this position's trial, else 0)
+    // the frame at the top moment: T_P = i^-P S_P (S_P: the sum CS already holds at this position's trial, else 0)
     const int rP = P & 3;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -1384,25 +1301,19 @@ __global__ __launch_bounds__(1 << (LN2 - 3)) __attribute__((amdgpu_waves_per_eu(
     const int m2 = (t & (Ns2 - 1)) * (N / (8 * Ns2)), m3 = (t & (Ns3 - 1)) * (N / (8 * Ns3)), m4 = t;
     const int z2 = (t / Ns2) * 8 * Ns2 + (t & (Ns2 - 1)), z3 = (t / Ns3) * 8 * Ns3 + (t & (Ns3 - 1));  // outputs
     // padded bases: element e = base + offset lands at e + e / 8 = (base + base / 8) + (offset + offset / 8 (+1 where
-    // the stage-2 offset 4 q carries into the base's bit 3 at LN2 = 11)) -- compile-time offsets
-    const int w1 = LN2 == 12 ? 9 * t : 4 * t + (t >> 1), w2 = z2 + (z2 >> 3), w3 = z3 + (z3 >> 3), rd = t + (t >> 3);
+    // the stage-2 offset 4 q carries into the base's bit 3)) -- compile-time offsets
+    const int w1 = 4 * t + (t >> 1), w2 = z2 + (z2 >> 3), w3 = z3 + (z3 >> 3), rd = t + (t >> 3);
     __syncthreads();  // tw
     // one moment: v (its row) through the four stages, moment p - 1's loads into nv, then the sum
     auto moment = [&](auto LAST, int p, double2 (&v)[8], double2 (&nv)[8], double2* A, double2* B) {
         constexpr bool last = decltype(LAST)::value;  // p == 0: w_0 = J_0 (1 where z = 0)
         if (p > plo) load_row(p - 1 - plo, nv);
-        if constexpr (LN2 == 12) {
-            nu_dft8(v);  // stage 1 (Ns = 1): element 8 t + q
+        nu_dft4(v[0], v[2], v[4], v[6]);  // stage 1 (R 4, Ns = 1): elements 4 t + q and 4 t + 1024 + q
+        nu_dft4(v[1], v[3], v[5], v[7]);
 #pragma unroll
-            for (int q = 0; q < 8; ++q) A[w1 + q] = v[q];
-        } else {
-            nu_dft4(v[0], v[2], v[4], v[6]);  // stage 1 (R 4, Ns = 1): elements 4 t + q and 4 t + 1024 + q
-            nu_dft4(v[1], v[3], v[5], v[7]);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                A[w1 + q] = v[2 * q];
-                A[w1 + N / 2 + N / 16 + q] = v[2 * q + 1];
-            }
+        for (int q = 0; q < 4; ++q) {
+            A[w1 + q] = v[2 * q];
+            A[w1 + N / 2 + N / 16 + q] = v[2 * q + 1];
         }
         __syncthreads();
 #pragma unroll
@@ -1410,7 +1321,7 @@ __global__ __launch_bounds__(1 << (LN2 - 3)) __attribute__((amdgpu_waves_per_eu(
         nu_twiddle<8>(nu_tw_tile(&tw, m2), v);
         nu_dft8(v);  // stage 2: element z2 + Ns2 q
 #pragma unroll
-        for (int q = 0; q < 8; ++q) B[w2 + Ns2 * q + (Ns2 == 8 ? q : q >> 1)] = v[q];
+        for (int q = 0; q < 8; ++q) B[w2 + Ns2 * q + (q >> 1)] = v[q];
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = B[rd + TPB * 9 / 8 * q];
@@ -1585,37 +1496,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
     nu_rows_epilogue<TPB, 8>(acc, k1b, ln1, nfft, jhi, h, tbase, r, nf, nbt, CS, F, nu_s, pos0);
 }
 
-// (C_k, S_k) of the trials of one harmonic: position pos = k1 n2 + k2 of the FFT output holds J = k1 + n1 k2
-// (ln1 = 0: natural order); J = jc mod n. The moments' transforms weighted by eps_p i^p J_p(pi jc / n) (nu_bes).
-__global__ __launch_bounds__(256) void k_nu_combine(const double2* __restrict__ Z, int lnfft, int ln1, int P, int nrow,
-                                                    int64_t nf, int64_t nseg, int64_t h, int64_t jbase, int64_t row0,
-                                                    int64_t tb0, int64_t nbt, const double* __restrict__ bc,
-                                                    double2* __restrict__ CS) {
-    const int64_t nfft = int64_t(1) << lnfft;
-    const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int row = blockIdx.y;
-    if (pos >= nfft) return;
-    const int ln2 = lnfft - ln1;
-    const int64_t J = (pos >> ln2) + ((pos & ((int64_t(1) << ln2) - 1)) << ln1);
-    int64_t jc;
-    if (J <= nseg - 1 - h)
-        jc = J;
-    else if (J >= nfft - h)
-        jc = J - nfft;
-    else
-        return;
-    const int64_t t = (row0 + row) * nf + jbase + jc - tb0;
-    if (t < 0 || t >= nbt) return;
-    const double zh = nu_zh(jc, lnfft);
-    double2 A = make_double2(0.0, 0.0);
-    NuBes bs = nu_bes_start(bc, P, zh);
-    for (int p = P - 1; p >= 0; --p) {  // sum_p eps_p i^p J_p(z) B_p (nu_bes_w)
-        const double2 b = Z[((int64_t)p * nrow + row) * nfft + pos];
-        A = nu_bes_acc(A, nu_bes_w(bs, p, zh), b, p);
-    }
-    CS[t] = A;
-}
-
 // Z^2 / H of trials tb0 .. tb0+nbt-1 (flat, relative to the call's first) from CS[k][t], in the reference's formula
 // order, with the certificate: |A_k error| <= E = N (2.4 (x/2)^P / P! + kNuRho), x = pi |jc| / n (invfact =
 // 2.4 / (2^P P!), nu_trunc), so Z2_k = (2/N)|A_k|^2
@@ -1644,7 +1524,8 @@ static int64_t g_last_nufft_n = 0;   // crimp_last_nufft_plan(): the last NUFFT'
 static int g_last_nufft_p = 0;       // and its spread form (1 cell gather, 0 MFMA slots)
 static int g_last_nufft_gather = 0;
 // Kernel classes of a NUFFT search (timed spans and work counts): cell starts, spread (cell gather or MFMA slots),
-// merge, FFT pass 1 (columns), FFT pass 2 (rows, with the Horner sum when fused), the separate Horner sum, finalize.
+// merge, FFT pass 1 (columns), FFT pass 2 (rows, with the moment sum), the separate moment sum (its kernel is removed:
+// the slot stays in the reporting ABI and holds 0), finalize.
 enum { kNuClsCellStart, kNuClsSpread, kNuClsMerge, kNuClsPass1, kNuClsPass2, kNuClsCombine, kNuClsFinalize, kNuCls };
 // crimp_last_nufft_work(): the last NUFFT's algorithmic work -- [0] spread fp64 flops, then HBM bytes per class 1..6
 // ([1] the spread's bytes; class 0, the cell starts, is not counted)
@@ -1797,16 +1678,6 @@ static int64_t nu_cus() {  // compute units of the current device (persistent gr
     return ncu;
 }
 
-// Moments per pass-1 / pass-2 chunk of the radix-8 row path (CRIMP_NUFFT_PCHUNK, an A/B hook read per call; unset, 0
-// or above P: one chunk, the whole moment set). Chunks meant the chunk's pass-1 output to be read back from the
-// Infinity Cache; measured slower at every size (config 3 pass 1 + pass 2: 0.265 ms whole, 0.352 at 8 moments, 0.527
-// at 4, 0.874 at 2; profiles/r06/ab_pchunk.log), so the default is one chunk.
-static int nu_pchunk() {
-    const char* e = getenv("CRIMP_NUFFT_PCHUNK");
-    const int c = e ? atoi(e) : 0;
-    return c > 0 ? c : (1 << 20);
-}
-
 // CRIMP_NUFFT_FINAL=separate: the k_nu_finalize launch after every row batch instead of the fused finalize (A/B and
 // identity test hook, read per call)
 static bool nu_final_separate() {
@@ -1836,8 +1707,7 @@ struct NuPlan {
 // n and P: among the powers of two n >= nseg (up to 2^24) whose edge truncation (nu_trunc) <= kNuEps within P <= pmax
 // moments, the one with the least FFT work n P; false when none exists or the photons wrap the grid more than
 // kNuMaxWrap times
-static bool nu_plan(NuPlan* pl, double delta, double f0, double dt0, double dtn, int nharm, int64_t nchunk, int pmax,
-                    double eps) {
+static bool nu_plan(NuPlan* pl, double delta, double f0, double dt0, double dtn, int nharm, int pmax, double eps) {
     // an ascending progression only: with delta < 0 the cells of the later photons come first (s1 < 0) and every
     // table below would be sized negative (a descending grid takes the exact rule)
     if (!(delta > 0.0) || !std::isfinite(delta) || !std::isfinite(f0)) return false;
@@ -1877,7 +1747,6 @@ static bool nu_plan(NuPlan* pl, double delta, double f0, double dt0, double dtn,
     const double glim = 2147483647.0 - (double)nfft;
     pl->gmin.assign((size_t)nharm, 0);
     pl->gmax.assign((size_t)nharm, 0);
-    (void)nchunk;
     for (int k = 1; k <= nharm; ++k) {
         const double a = (double)k * u0, b = (double)k * un;
         if (!(std::fabs(a) < glim && std::fabs(b) < glim)) return false;  // NaN declines too
@@ -1974,6 +1843,86 @@ static void nu_spec_store(const NuSpecKey& k, const double* hs) {
     g_nu_spec.push_back(e);
 }
 
+// Row groups of trials [first, first + count): the first row's segment, the full rows between, the last row's
+// segment, each planned (nu_plan for nharm + 1 harmonics: an MFMA spread pass may run one past nharm). False when a
+// segment is shorter than 64 trials or has no plan.
+static bool nu_row_groups(std::vector<NuPlan>* plans, int64_t first, int64_t count, int64_t nf, double delta, double f0,
+                          double dt0, double dtn, int nharm, int pmax, double eps) {
+    const int64_t r_lo = first / nf, r_hi = (first + count - 1) / nf;
+    for (int64_t r = r_lo; r <= r_hi;) {
+        const int64_t a = std::max<int64_t>(first, r * nf) - r * nf, b = std::min<int64_t>(first + count, (r + 1) * nf) - r * nf;
+        int64_t r1 = r + 1;
+        if (a == 0 && b == nf)
+            while (r1 <= r_hi && std::min<int64_t>(first + count, (r1 + 1) * nf) - r1 * nf == nf) ++r1;
+        NuPlan pl;
+        pl.r0 = r;
+        pl.r1 = r1;
+        pl.j0 = a;
+        pl.nseg = b - a;
+        if (pl.nseg < 64 || !nu_plan(&pl, delta, f0, dt0, dtn, nharm + 1, pmax, eps)) return false;
+        plans->push_back(std::move(pl));
+        r = r1;
+    }
+    return true;
+}
+
+// The MFMA spread's passes, (k0, harmonics) each, and the bytes of their largest slot array. Harmonics per pass: the
+// largest size in {10, 8, 6, 4, 2} (<= Gmax) the remaining harmonics fill, allowing one past nharm (its cells are
+// planned, nu_row_groups): H_20 runs as 10 + 10 (two photon passes; 8 + 8 + 4 paid the per-photon phase and cis three
+// times). Gmax: the largest of 10, 8, 4, 2 whose slots fit the budget beside the fixed_bytes of W, Y and the sums.
+static int64_t nu_spread_passes(std::vector<std::pair<int, int>>* passes, const std::vector<NuPlan>& plans, int nharm,
+                                int64_t nchunk, int64_t fixed_bytes) {
+    int64_t ubytes = 0;
+    for (int Gmax = 10;; Gmax = Gmax == 10 ? 8 : Gmax / 2) {  // Gmax >= 2
+        passes->clear();
+        ubytes = 0;
+        for (int k0 = 1; k0 <= nharm;) {
+            const int rem = nharm - k0 + 1;
+            int gl = 2;
+            for (int cand : {10, 8, 6, 4, 2})
+                if (cand <= Gmax && cand <= rem + 1) {
+                    gl = cand;
+                    break;
+                }
+            for (const NuPlan& pl : plans) {
+                const int64_t SLmax = 2 * (int64_t)pl.P * std::min<int64_t>(kNuRows, pl.r1 - pl.r0);
+                int64_t sl = 0;
+                for (int k = k0; k < k0 + gl; ++k)
+                    sl += (pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 1 + nchunk) * SLmax;
+                ubytes = std::max<int64_t>(ubytes, sl * 8);
+            }
+            passes->emplace_back(k0, gl);
+            k0 += gl;
+        }
+        if (Gmax == 2 || ubytes + fixed_bytes <= nufft_budget()) break;
+    }
+    return ubytes;
+}
+
+// CRIMP_NUFFT_ROWS4096=0: every FFT by the generic kernels (k_nu_fft_cols, k_nu_fft_rows_combine, k_nu_finalize) -- the
+// reference the specialised column and row kernels are tested against, read per call
+static bool nu_generic_fft() {
+    const char* e = getenv("CRIMP_NUFFT_ROWS4096");
+    return e && !strcmp(e, "0");
+}
+
+// The radix-8 row kernels' dynamic LDS (above the 64 KB default), set once per device
+static int nu_rows_lds_attrs() {
+    static std::mutex mu;
+    static uint64_t done = 0;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    if (dev >= 64 || !(done >> dev & 1)) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nu_rows_iw),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kNuTile * (int)sizeof(double2)));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nu_rows_combine8<11>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)nu_rows_lds(11)));
+        if (dev < 64) done |= uint64_t(1) << dev;
+    }
+    return CRIMP_OK;
+}
+
 static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, int64_t n, const double* freq,
                         int64_t nf, int64_t nrows_grid, const double* c2, const double* hs, bool twod, int nharm,
                         int stat, int64_t first,
@@ -1992,25 +1941,10 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
     // slots otherwise -- decided from the whole grid, so that row shards compute exactly what the whole grid does
     // (CRIMP_NUFFT_SPREAD=gather|mfma forces one, a test hook)
     const bool gather_grid = nu_gather_form(nrows_grid);
-    // row groups: the first row's segment, the full rows between, the last row's segment
-    const int64_t r_lo = first / nf, r_hi = (first + count - 1) / nf;
     std::vector<NuPlan> plans;
-    for (int64_t r = r_lo; r <= r_hi;) {
-        const int64_t a = std::max<int64_t>(first, r * nf) - r * nf, b = std::min<int64_t>(first + count, (r + 1) * nf) - r * nf;
-        int64_t r1 = r + 1;
-        if (a == 0 && b == nf)
-            while (r1 <= r_hi && std::min<int64_t>(first + count, (r1 + 1) * nf) - r1 * nf == nf) ++r1;
-        NuPlan pl;
-        pl.r0 = r;
-        pl.r1 = r1;
-        pl.j0 = a;
-        pl.nseg = b - a;
-        if (pl.nseg < 64 || !nu_plan(&pl, delta, f0, dt0, dtn, nharm + 1, nchunk, gather_grid ? kNuGatherMaxP : kNuMaxP,
-                                     stat == 0 && nharm >= 2 ? kNuEpsZm : kNuEps))
-            return CRIMP_OK;
-        plans.push_back(std::move(pl));
-        r = r1;
-    }
+    if (!nu_row_groups(&plans, first, count, nf, delta, f0, dt0, dtn, nharm, gather_grid ? kNuGatherMaxP : kNuMaxP,
+                       stat == 0 && nharm >= 2 ? kNuEpsZm : kNuEps))
+        return CRIMP_OK;
     *applicable = true;
     g_last_search_path = 2;
     g_last_nufft_n = 0;
@@ -2021,8 +1955,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
         }
     g_last_nufft_gather = gather_grid ? 1 : 0;
     for (double& w : g_nu_work) w = 0.0;
-    // buffers sized for the largest group; harmonics per spread pass: the largest G in {8, 4, 2, 1} whose slots fit
-    // the budget beside W, Y and the sums
+    // buffers sized for the largest group
     int64_t Bmax = 0, nfmax = 0, csmax = 0, nrow_all = 0;
     for (const NuPlan& pl : plans) {
         const int64_t nrow_max = std::min<int64_t>(kNuRows, pl.r1 - pl.r0);
@@ -2039,90 +1972,24 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
         while (gw > 1 && (gw + 1) * Bmax * 16 + csmax * 16 > nufft_budget()) --gw;
     }
     const int64_t fixed_bytes = (gw + 1) * Bmax * 16 + csmax * 16;
-    std::vector<std::pair<int, int>> passes;  // (k0, harmonics) of each spread pass, harmonics a power of two
-    int64_t ubytes = 0;
-    // harmonics per MFMA spread pass: the largest size in {10, 8, 6, 4, 2} (<= Gmax) the remaining harmonics fill,
-    // allowing one past nharm (its cells are planned, nu_plan(nharm + 1)): H_20 runs as 10 + 10 (two photon passes;
-    // 8 + 8 + 4 paid the per-photon phase and cis three times)
-    for (int Gmax = 10;; Gmax = Gmax == 10 ? 8 : Gmax / 2) {  // Gmax >= 2
-        const int G = Gmax;
-        passes.clear();
-        ubytes = 0;
-        for (int k0 = 1; k0 <= nharm;) {
-            const int rem = nharm - k0 + 1;
-            int gl = 2;
-            for (int cand : {10, 8, 6, 4, 2})
-                if (cand <= G && cand <= rem + 1) {
-                    gl = cand;
-                    break;
-                }
-            for (const NuPlan& pl : plans) {
-                const int64_t SLmax = 2 * (int64_t)pl.P * std::min<int64_t>(kNuRows, pl.r1 - pl.r0);
-                int64_t sl = 0;
-                for (int k = k0; k < k0 + gl; ++k)
-                    sl += (pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 1 + nchunk) * SLmax;
-                ubytes = std::max<int64_t>(ubytes, sl * 8);
-            }
-            passes.emplace_back(k0, gl);
-            k0 += gl;
-        }
-        if (G == 2 || ubytes + fixed_bytes <= nufft_budget()) break;
-    }
-    auto use_gather = [&](const NuPlan&) { return gather_grid; };
-    // pass 2 fused with the combine (default); CRIMP_NUFFT_FUSED=0 runs them as two kernels (A/B hook)
-    const char* fused_env = getenv("CRIMP_NUFFT_FUSED");
-    const bool fused_combine = !(fused_env && !strcmp(fused_env, "0"));
-    // CRIMP_NUFFT_ROWS4096=0 runs 4096-element rows and 256-element columns through the generic kernels (A/B and
-    // identity test hook)
-    const char* r4_env = getenv("CRIMP_NUFFT_ROWS4096");
-    const bool rows4096 = !(r4_env && !strcmp(r4_env, "0"));
-    // pass 2 of 4096-element rows by the 512-thread radix-8 kernel (default: 0.178 vs 0.190 ms per config-3 search,
-    // profiles/r05/ab_r8_ilp.log); CRIMP_NUFFT_R8=0 runs the radix-16 form
-    const char* r8_env = getenv("CRIMP_NUFFT_R8");
-    const bool rows_r8 = !(r8_env && !strcmp(r8_env, "0"));
-    // CRIMP_NUFFT_ROW2048=1: n = 2^20 as 512 x 2048 (k_nu_cols512, k_nu_rows_combine8<11>), else 256 x 4096. The row
-    // pass gains what the column pass loses (config 3: pass 2 0.160 vs 0.180 ms, pass 1 0.138 vs 0.115 ms per search,
-    // profiles/r06/ab_rows2048_cols512.log), so 4096-element rows stay the default.
-    const char* r2k_env = getenv("CRIMP_NUFFT_ROW2048");
-    const bool row2048 = r2k_env && !strcmp(r2k_env, "1") && rows4096 && rows_r8 && fused_combine;
-    auto row_log = [&](int lnfft) { return row2048 && lnfft == 20 ? 11 : std::min(lnfft, 12); };
-    // 4096-element rows by k_nu_rows_iw (one cross-wave exchange per moment; 0.171 vs 0.180 ms per config-3 search,
-    // profiles/r06/ab_p2_iw.log); CRIMP_NUFFT_P2_IW=0: k_nu_rows_combine8<12> (three block-wide exchanges)
-    const char* iw_env = getenv("CRIMP_NUFFT_P2_IW");
-    const bool p2_iw = !(iw_env && !strcmp(iw_env, "0"));
-    {  // 128 KB of dynamic LDS for k_nu_rows4096_combine, set once per device
-        static std::mutex mu;
-        static uint64_t done = 0;
-        int dev = 0;
-        HIPCHK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev >= 64 || !(done >> dev & 1)) {
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nu_rows4096_combine),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kNuTile * (int)sizeof(double2)));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nu_rows_combine8<12>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)nu_rows_lds(12)));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nu_rows_iw),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kNuTile * (int)sizeof(double2)));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_nu_rows_combine8<11>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)nu_rows_lds(11)));
-            if (dev < 64) done |= uint64_t(1) << dev;
-        }
+    std::vector<std::pair<int, int>> passes;  // (k0, harmonics) of each MFMA spread pass
+    const int64_t ubytes = nu_spread_passes(&passes, plans, nharm, nchunk, fixed_bytes);
+    const bool generic_fft = nu_generic_fft();
+    {
+        const int rc = nu_rows_lds_attrs();
+        if (rc) return rc;
     }
     const char* lanes_s = getenv("CRIMP_NUFFT_LANES");
     const int lanes_env = lanes_s ? atoi(lanes_s) : 0;
     ARGCHK(lanes_env == 0 || lanes_env == 1 || lanes_env == 2 || lanes_env == 4 || lanes_env == 8,
            "CRIMP_NUFFT_LANES must be 1, 2, 4 or 8");
-    bool any_mfma = false;
-    int64_t starts_max = 0;
-    for (const NuPlan& pl : plans) {
-        if (!use_gather(pl)) {
-            any_mfma = true;
-            continue;
+    int64_t starts_max = 0;  // the cell gather's start tables of the largest group
+    if (gather_grid)
+        for (const NuPlan& pl : plans) {
+            int64_t tot = 0;
+            for (int k = 1; k <= nharm; ++k) tot += pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 2;
+            starts_max = std::max<int64_t>(starts_max, tot);
         }
-        int64_t tot = 0;
-        for (int k = 1; k <= nharm; ++k) tot += pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 2;
-        starts_max = std::max<int64_t>(starts_max, tot);
-    }
     double* U = nullptr;
     double2 *W = nullptr, *Y = nullptr, *CS = nullptr;
     int64_t* ctab = nullptr;
@@ -2130,7 +1997,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
     int64_t* flagged = nullptr;
     // nflag: [fix-up count, photons out of order (1; cell-gather plans) or a cached plan no longer valid (2), -, -,
     // best power, best index (as doubles)], zeroed or set by k_ap_final, read back in one transfer at the end
-    if (any_mfma) {
+    if (!gather_grid) {
         HIPCHK(sc.alloc(&U, (size_t)(ubytes / 8)));
         HIPCHK(sc.alloc(&ctab, (size_t)(2 * kNuPassMax * nchunk)));
     }
@@ -2139,19 +2006,18 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
     HIPCHK(sc.alloc(&Y, (size_t)Bmax));
     HIPCHK(sc.alloc(&CS, (size_t)csmax));
     HIPCHK(sc.alloc(&flagged, (size_t)count));
-    // per-block best trials of the fused finalize (k_nu_rows_combine8 blocks of every row batch)
+    // per-block best trials of the fused finalize (the radix-8 row pass's blocks of every row batch)
     BestCand* best_part = nullptr;
     int64_t best_count = 0, separate_batches = 0;
     if (best) {
         int64_t nb = 0;
-        for (const NuPlan& pl : plans) nb += (pl.r1 - pl.r0) * (int64_t(1) << (pl.lnfft - row_log(pl.lnfft)));
+        for (const NuPlan& pl : plans) nb += (pl.r1 - pl.r0) * (int64_t(1) << (pl.lnfft - std::min(pl.lnfft, 12)));
         HIPCHK(sc.alloc(&best_part, (size_t)std::max<int64_t>(nb, 1)));
     }
     // every MFMA (group, row batch, pass)'s slot table, uploaded once before the launches
     std::vector<NuPass> hps;
     for (const NuPlan& pl : plans) {
-        if (use_gather(pl)) continue;
-        for (int64_t rb = pl.r0; rb < pl.r1; rb += kNuRows) {
+        for (int64_t rb = pl.r0; !gather_grid && rb < pl.r1; rb += kNuRows) {
             const int64_t SL = 2 * (int64_t)pl.P * std::min<int64_t>(kNuRows, pl.r1 - rb);
             for (const auto& pass : passes) {
                 NuPass ps{};
@@ -2203,141 +2069,80 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
         if (ev.empty()) HIPCHK(mark());
         const int lnfft = pl.lnfft, P = pl.P;
         const int64_t nfft = int64_t(1) << lnfft;
-        // FFT shape: one row pass for n <= kNuTile (2^lrow transforms per block), else columns (n1 = n / 4096 <= 4096)
-        // then rows of 4096
-        const int ln2 = row_log(lnfft), ln1 = lnfft - ln2;
+        // FFT shape: one row pass for n <= kNuTile, else columns (n1 = n / 4096 <= 4096) then rows of 4096
+        const int ln2 = std::min(lnfft, 12), ln1 = lnfft - ln2;
         const int lcol = 12 - ln1;  // columns per block in pass 1 (n1 * c = 4096)
-        const int lrow = 12 - ln2;  // rows per block in pass 2
         const int64_t jbase = pl.j0 + pl.h;
-        // W (moments of harmonic k, rows [rb, rb + nrow)) -> FFT -> (C_k, S_k) of the batch's trials
         auto occupied = [&](int k, int* alo, int* acnt) {
             nu_occupied(pl.gmin[(size_t)(k - 1)], pl.gmax[(size_t)(k - 1)], lnfft, ln1, alo, acnt);
         };
-        // fused finalize: the last harmonic's row pass forms the powers (NuFinal), for the 4096-row radix-8 path
-        const bool fuse_final = fused_combine && ln2 >= 11 && rows4096 && rows_r8 && !nu_final_separate();
+        // the radix-8 row kernels (rows of 2048 and 4096) finalize in the last harmonic's launch (NuFinal)
+        const bool fuse_final = ln2 >= 11 && !generic_fft && !nu_final_separate();
         bool final_done = false;  // set by fft_combine when it finalized the batch
-        auto fft_combine = [&](int k, int64_t rb, int nrow, int64_t tb0, int64_t nbt, double2* W) -> int {
+        // W (moments of harmonic k, rows [rb, rb + nrow)) -> FFT -> (C_k, S_k) of the batch's trials: columns by ln1,
+        // rows by ln2, the generic kernel of each wherever no specialised one exists (or generic_fft)
+        auto fft_combine = [&](int k, int64_t rb, int nrow, int64_t tb0, int64_t nbt, const double2* W) -> int {
             const int64_t Bp = (int64_t)P * nrow;
             const double plane = 16.0 * (double)Bp * (double)nfft;  // one complex FFT buffer of the batch
-            if (fused_combine && ln2 >= 11 && rows4096 && rows_r8) {
-                // moment chunks of <= nu_pchunk() (default: all P moments in one): pass 1 and pass 2 of a chunk in turn
-                int alo = 0, acnt = 0;
-                if (ln1 > 0) occupied(k, &alo, &acnt);
-                const int pc = std::max(1, std::min(nu_pchunk(), P));
-                for (int phi = P; phi > 0; phi -= pc) {
-                    const int plo = std::max(0, phi - pc);
-                    const int64_t Bc = (int64_t)(phi - plo) * nrow;
-                    const double cplane = 16.0 * (double)Bc * (double)nfft;
-                    const double2* Win = W + (int64_t)plo * nrow * nfft;
-                    const double2* Zo = Win;
-                    if (ln1 > 0) {
-                        g_nu_work[kNuClsPass1] += cplane * ((double)acnt / (double)(int64_t(1) << ln1)) + cplane;
-                        if (ln1 == 8) {
-                            const int64_t ngroups = Bc << (ln2 - 4);
-                            k_nu_cols256<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 256, lds_fft, s>>>(
-                                Win, Y, lnfft, T, alo, acnt, ngroups);
-                        } else if (ln1 == 9) {
-                            const int64_t ngroups = Bc << (ln2 - 3);
-                            k_nu_cols512<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 512, lds_fft, s>>>(
-                                Win, Y, lnfft, T, alo, acnt, ngroups);
-                        } else {
-                            k_nu_fft_cols<<<dim3((unsigned)(int64_t(1) << (ln2 - lcol)), (unsigned)Bc), 256, lds_fft,
-                                            s>>>(Win, Y, lnfft, ln1, lcol, T, alo, acnt);
-                        }
-                        HIPCHK(hipGetLastError());
-                        Zo = Y;
-                        HIPCHK(span(kNuClsPass1));
-                    }
-                    NuFinal F{};
-                    if (fuse_final && k == nharm && plo == 0) {
-                        F.on = 1;
-                        F.m = nharm;
-                        F.stat = stat;
-                        F.Pc = P;
-                        F.nph = (double)n;
-                        F.invfact = pl.invfact;
-                        F.rel = fixup_rel();
-                        F.tb0 = tb0;
-                        F.out = out;
-                        F.nflag = nflag;
-                        F.flagged = flagged;
-                        F.best_part = best ? best_part : nullptr;
-                        F.best_base = best_count;
-                        F.CS0 = CS;
-                        best_count += (int64_t(1) << ln1) * nrow;
-                        final_done = true;
-                    }
-                    // bytes: the chunk's planes; CS read by a later chunk and written, or (fused finalize) the
-                    // earlier harmonics' sums read and the powers written
-                    g_nu_work[kNuClsPass2] += cplane + (F.on ? (16.0 * (nharm - 1) + 8.0) * (double)nbt
-                                                             : 16.0 * (double)nbt * (phi < P ? 2.0 : 1.0));
-                    const dim3 g2((unsigned)(int64_t(1) << ln1), (unsigned)nrow);
-                    if (ln2 == 12 && p2_iw)
-                        k_nu_rows_iw<<<g2, 512, 2 * lds_fft, s>>>(
-                            Zo, lnfft, phi, plo, phi < P ? 1 : 0, nrow, nf, pl.nseg - 1 - pl.h, pl.h,
-                            rb * nf + jbase - (tb0 + first), nbt, bc, CS + (int64_t)(k - 1) * nbt, F);
-                    else if (ln2 == 11)
-                        k_nu_rows_combine8<11><<<g2, 256, nu_rows_lds(11), s>>>(
-                            Zo, lnfft, phi, plo, phi < P ? 1 : 0, nrow, nf, pl.nseg - 1 - pl.h, pl.h,
-                            rb * nf + jbase - (tb0 + first), nbt, bc, CS + (int64_t)(k - 1) * nbt, F);
-                    else
-                        k_nu_rows_combine8<12><<<g2, 512, nu_rows_lds(12), s>>>(
-                            Zo, lnfft, phi, plo, phi < P ? 1 : 0, nrow, nf, pl.nseg - 1 - pl.h, pl.h,
-                            rb * nf + jbase - (tb0 + first), nbt, bc, CS + (int64_t)(k - 1) * nbt, F);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(span(kNuClsPass2));
-                }
-                return CRIMP_OK;
-            }
-            double2* Zo = W;
+            const double2* Z = W;
             if (ln1 > 0) {
                 int alo = 0, acnt = 0;
                 occupied(k, &alo, &acnt);
                 g_nu_work[kNuClsPass1] += plane * ((double)acnt / (double)(int64_t(1) << ln1)) + plane;  // occupied rows in, all out
-                if (ln1 == 8 && rows4096) {
+                if (ln1 == 8 && !generic_fft) {
                     const int64_t ngroups = Bp << (ln2 - 4);
                     k_nu_cols256<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 256, lds_fft, s>>>(
                         W, Y, lnfft, T, alo, acnt, ngroups);
-                    HIPCHK(hipGetLastError());
+                } else if (ln1 == 9 && !generic_fft) {
+                    const int64_t ngroups = Bp << (ln2 - 3);
+                    k_nu_cols512<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 512, lds_fft, s>>>(
+                        W, Y, lnfft, T, alo, acnt, ngroups);
                 } else {
                     k_nu_fft_cols<<<dim3((unsigned)(int64_t(1) << (ln2 - lcol)), (unsigned)Bp), 256, lds_fft, s>>>(
                         W, Y, lnfft, ln1, lcol, T, alo, acnt);
-                    HIPCHK(hipGetLastError());
                 }
-                Zo = Y;
+                HIPCHK(hipGetLastError());
+                Z = Y;
                 HIPCHK(span(kNuClsPass1));
             }
-            if (fused_combine && ln2 == 12 && rows4096) {  // the specialised form for 4096-element rows
-                g_nu_work[kNuClsPass2] += plane + 16.0 * (double)nbt;
-                k_nu_rows4096_combine<<<dim3((unsigned)(int64_t(1) << ln1), (unsigned)nrow), 256, 2 * lds_fft, s>>>(
-                    Zo, lnfft, P, nrow, nf, pl.nseg - 1 - pl.h, pl.h, rb * nf + jbase - (tb0 + first), nbt, bc,
-                    CS + (int64_t)(k - 1) * nbt);
-                HIPCHK(hipGetLastError());
-                HIPCHK(span(kNuClsPass2));
-                return CRIMP_OK;
+            NuFinal F{};
+            if (fuse_final && k == nharm) {
+                F.on = 1;
+                F.m = nharm;
+                F.stat = stat;
+                F.Pc = P;
+                F.nph = (double)n;
+                F.invfact = pl.invfact;
+                F.rel = fixup_rel();
+                F.tb0 = tb0;
+                F.out = out;
+                F.nflag = nflag;
+                F.flagged = flagged;
+                F.best_part = best ? best_part : nullptr;
+                F.best_base = best_count;
+                F.CS0 = CS;
+                best_count += (int64_t(1) << ln1) * nrow;
+                final_done = true;
             }
-            if (fused_combine) {  // pass 2 and the moments' Horner sum in one kernel
-                g_nu_work[kNuClsPass2] += plane + 16.0 * (double)nbt;
-                k_nu_fft_rows_combine<<<dim3((unsigned)(int64_t(1) << ln1), (unsigned)nrow), 256, lds_fft, s>>>(
-                    Zo, ln2, lnfft, P, nrow, nf, pl.nseg - 1 - pl.h, pl.h, rb * nf + jbase - (tb0 + first), nbt, bc,
-                    CS + (int64_t)(k - 1) * nbt);
-                HIPCHK(hipGetLastError());
-                HIPCHK(span(kNuClsPass2));
-                return CRIMP_OK;
-            }
-            g_nu_work[kNuClsPass2] += 2.0 * plane;
-            g_nu_work[kNuClsCombine] += plane + 16.0 * (double)nbt;
-            k_nu_fft_rows<<<(unsigned)cdiv(Bp << ln1, int64_t(1) << lrow), 256, lds_fft, s>>>(Zo, ln2, lrow, lnfft);
+            // bytes: the moments' planes read; the sums written, or (fused finalize) the earlier harmonics' sums read
+            // and the powers written
+            g_nu_work[kNuClsPass2] += plane + (F.on ? (16.0 * (nharm - 1) + 8.0) * (double)nbt : 16.0 * (double)nbt);
+            const dim3 g2((unsigned)(int64_t(1) << ln1), (unsigned)nrow);
+            const int64_t jhi = pl.nseg - 1 - pl.h, tbase = rb * nf + jbase - (tb0 + first);
+            double2* CSk = CS + (int64_t)(k - 1) * nbt;
+            // plo = 0, accum = 0: all P moments in the one launch, the sum from zero (see the row kernels' comment)
+            if (ln2 == 12 && !generic_fft)
+                k_nu_rows_iw<<<g2, 512, 2 * lds_fft, s>>>(Z, lnfft, P, 0, 0, nrow, nf, jhi, pl.h, tbase, nbt, bc, CSk, F);
+            else if (ln2 == 11 && !generic_fft)
+                k_nu_rows_combine8<11><<<g2, 256, nu_rows_lds(11), s>>>(Z, lnfft, P, 0, 0, nrow, nf, jhi, pl.h, tbase, nbt,
+                                                                         bc, CSk, F);
+            else
+                k_nu_fft_rows_combine<<<g2, 256, lds_fft, s>>>(Z, ln2, lnfft, P, nrow, nf, jhi, pl.h, tbase, nbt, bc, CSk);
             HIPCHK(hipGetLastError());
             HIPCHK(span(kNuClsPass2));
-            k_nu_combine<<<dim3((unsigned)cdiv(nfft, 256), (unsigned)nrow), 256, 0, s>>>(
-                Zo, lnfft, ln1, P, nrow, nf, pl.nseg, pl.h, jbase, rb, tb0 + first, nbt, bc,
-                CS + (int64_t)(k - 1) * nbt);
-            HIPCHK(hipGetLastError());
-            HIPCHK(span(kNuClsCombine));
             return CRIMP_OK;
         };
-        auto finalize = [&](int64_t tb0, int64_t nbt) -> int {
+        auto finalize =[&](int64_t tb0, int64_t nbt) -> int {
             g_nu_work[kNuClsFinalize] += 16.0 * (double)nharm * (double)nbt + 8.0 * (double)nbt;
             k_nu_finalize<<<(unsigned)cdiv(nbt, 256), 256, 0, s>>>(CS, nbt, nharm, stat, (double)n, nf, jbase, nfft, P,
                                                                    pl.invfact, fixup_rel(), tb0, first, out, nflag,
@@ -2346,7 +2151,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
             HIPCHK(span(kNuClsFinalize));
             return CRIMP_OK;
         };
-        if (use_gather(pl)) {
+        if (gather_grid) {
             std::vector<int64_t> soff((size_t)nharm);
             int64_t off = 0;
             // no zeroing of the start tables: on time-sorted photons every entry is written (each cell's first
@@ -2363,14 +2168,10 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
                     off += ca.span[j] + 1;
                 }
                 const unsigned cb = (unsigned)std::min<int64_t>(cdiv(cdiv(n, 2), 256 * kNuCellU), 2048);
-                // CRIMP_NUFFT_CS_MODE (A/B probe of the pass's cost): 1 = loads and order check only (the search is
-                // discarded), 2 = no block barrier; 0 = the pass
-                const char* csm = getenv("CRIMP_NUFFT_CS_MODE");
-                const int cs_mode = csm ? atoi(csm) : 0;
                 if ((reinterpret_cast<uintptr_t>(t) & 15u) == 0)
-                    k_nu_cellstart<true><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1, cs_mode);
+                    k_nu_cellstart<true><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1);
                 else
-                    k_nu_cellstart<false><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1, cs_mode);
+                    k_nu_cellstart<false><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1);
                 HIPCHK(hipGetLastError());
             }
             HIPCHK(span(kNuClsCellStart));

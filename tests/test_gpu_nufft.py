@@ -206,13 +206,12 @@ def test_nufft_declines_cells_beyond_32_bits(gpu):
     close_rel(zm, ops.search(t, tm, f, 2, 0, precision="f64"))
 
 
-def test_nufft_fused_pass2_equals_separate_combine(gpu, monkeypatch):
-    """FFT pass 2 fused with the moments' Horner sum against pass 2 and k_nu_combine as two kernels
-    (CRIMP_NUFFT_FUSED=0), both with the radix-16 row transform (CRIMP_NUFFT_R8=0): the same arithmetic, so
-    bit-identical powers; the default (512-thread radix-8 row pass, k_nu_rows_iw) and the 4096-row / 256-row-column
-    kernels (k_nu_rows4096_combine, k_nu_rows_combine8, k_nu_cols256; k_nu_cols512 with 2048-element rows at n = 2^20) against
-    the generic ones (CRIMP_NUFFT_ROWS4096=0) to rounding -- single-pass (n <= 4096) and four-step FFTs, 1-D and 2-D
-    grids."""
+def test_nufft_specialised_fft_kernels_equal_generic(gpu, monkeypatch):
+    """The default FFT dispatch -- the radix-8 row passes k_nu_rows_combine8<11> (n = 2^11) and k_nu_rows_iw (rows of
+    4096) with their fused finalize, the columns k_nu_fft_cols, k_nu_cols256 (n = 2^20) and k_nu_cols512 (n = 2^21)
+    -- against the generic kernels of every size (CRIMP_NUFFT_ROWS4096=0: k_nu_fft_cols, k_nu_fft_rows_combine,
+    k_nu_finalize) to rounding, on raw powers (fix-up off): single-pass and four-step FFTs, 1-D and 2-D grids, both
+    spread forms. Each case's plan size is asserted, so every kernel family stays pinned to a shape."""
     from crimp_amd import ops, _native as N
     from crimp_amd.synth import pulsed_events
     t = pulsed_events(200000, 2.0e5, 3.3, pulsed_frac=0.05, fdot=-2e-11, seed=8)
@@ -225,23 +224,20 @@ def test_nufft_fused_pass2_equals_separate_combine(gpu, monkeypatch):
         z = ops.search(t, t0, f, m, 1, log10_negfdot=fdv, precision="nufft", flags=N.FLAG_NO_FIXUP)
         for k in env:
             monkeypatch.delenv(k)
+        assert _path() == 2
+        assert N.last_nufft_plan()[0] == 1 << ln, (N.last_nufft_plan(), ln)
         return z
 
     def close(x, y):
         rel = np.abs(x - y) / np.abs(y)
         assert rel.max() <= 1e-10 and np.median(rel) <= 1e-13, (rel.max(), np.median(rel))
 
-    for f, m, fdv in ((3.3 + np.arange(-700, 701) / 2.0e6, 2, None), (3.3 + np.arange(-40000, 40000) / 2.0e6, 3, None),
-                      (3.3 + np.arange(-1500, 1500) / 2.0e6, 5, fd),
-                      (3.3 + np.arange(-300000, 300000) / 2.0e7, 2, None)):  # n = 2^20: 256-row columns
-        r16 = run(CRIMP_NUFFT_R8="0")
-        np.testing.assert_array_equal(r16, run(CRIMP_NUFFT_R8="0", CRIMP_NUFFT_FUSED="0"))
-        generic = run(CRIMP_NUFFT_ROWS4096="0")
-        close(r16, generic)
-        close(run(), generic)
-        close(run(CRIMP_NUFFT_P2_IW="0"), generic)  # three block-wide exchanges per moment (k_nu_rows_combine8<12>)
-        if len(f) == 600000:  # n = 2^20 as 512 x 2048 (k_nu_cols512, k_nu_rows_combine8<11>)
-            close(run(CRIMP_NUFFT_ROW2048="1"), generic)
+    for f, m, fdv, ln in ((3.3 + np.arange(-700, 701) / 2.0e6, 2, None, 11),           # k_nu_rows_combine8<11>
+                          (3.3 + np.arange(-40000, 40000) / 2.0e6, 3, None, 17),       # k_nu_fft_cols + k_nu_rows_iw
+                          (3.3 + np.arange(-1500, 1500) / 2.0e6, 5, fd, 12),           # MFMA spread, k_nu_rows_iw
+                          (3.3 + np.arange(-300000, 300000) / 2.0e7, 2, None, 20),     # k_nu_cols256
+                          (3.3 + np.arange(-600000, 600000) / 2.0e7, 2, None, 21)):    # k_nu_cols512
+        close(run(), run(CRIMP_NUFFT_ROWS4096="0"))
 
 
 def test_nufft_gather_lane_splits(gpu, monkeypatch):
@@ -270,11 +266,9 @@ def test_nufft_gather_lane_splits(gpu, monkeypatch):
         ops.search(t, t0, f, 2, 1, precision="nufft")
 
 
-def test_nufft_moment_chunks_agree(gpu, monkeypatch):
-    """The radix-8 row path runs the moments in chunks (CRIMP_NUFFT_PCHUNK, default 4: pass 1 and pass 2 of one chunk
-    in turn, each chunk adding its part of the moment sum to the trials' harmonic sums): chunks of 1, 3, 4 and all P
-    moments agree to rounding (the chunks restart the Bessel recurrence from their own series values) -- a 1-D
-    2^20-point plan (256-row columns) and a 2-D 2^17-point plan (generic columns), raw powers (fix-up off)."""
+def test_nufft_four_step_raw_powers_vs_f64(gpu):
+    """The default search's four-step FFTs against the fp64 kernel on every trial, raw powers (fix-up off): a 1-D
+    2^20-point plan (256-row columns) and a 2-D 2^17-point plan (generic columns), both with rows of 4096."""
     from crimp_amd import ops, _native as N
     from crimp_amd.synth import pulsed_events
     t = pulsed_events(300_000, 2.0e5, 3.3, pulsed_frac=0.05, fdot=-2e-11, seed=13)
@@ -282,15 +276,9 @@ def test_nufft_moment_chunks_agree(gpu, monkeypatch):
     cases = ((3.3 + np.arange(-300000, 300000) / 2.0e7, 2, None), (3.3 + np.arange(-40000, 40000) / 2.0e6, 3,
                                                                     np.array([-12.0, -11.0, -10.5])))
     for f, m, fdv in cases:
-        got = {}
-        for pc in ("0", "1", "3", "4"):
-            monkeypatch.setenv("CRIMP_NUFFT_PCHUNK", pc)
-            got[pc] = ops.search(t, t0, f, m, 1, log10_negfdot=fdv, flags=N.FLAG_NO_FIXUP)
-            assert _path() == 2
-        for pc in ("1", "3", "4"):
-            rel = np.abs(got[pc] - got["0"]) / np.abs(got["0"])
-            assert rel.max() <= 1e-10 and np.median(rel) <= 1e-13, (pc, rel.max(), np.median(rel))
-        close_rel(got["4"], ops.search(t, t0, f, m, 1, log10_negfdot=fdv, precision="f64"), 1e-6)
+        got = ops.search(t, t0, f, m, 1, log10_negfdot=fdv, flags=N.FLAG_NO_FIXUP)
+        assert _path() == 2
+        close_rel(got, ops.search(t, t0, f, m, 1, log10_negfdot=fdv, precision="f64"), 1e-6)
 
 
 @pytest.mark.parametrize("rows", [1, 3])

@@ -27,19 +27,20 @@ t = torch.as_tensor(t_h, device=dev)
 f = torch.as_tensor(f_h, device=dev)
 t0 = (t_h[0] + t_h[-1]) / 2
 variants = {"auto": {}, "mfma": {"CRIMP_NUFFT_SPREAD": "mfma"}, "lanes1": {"CRIMP_NUFFT_LANES": "1"},
-            "nofused": {"CRIMP_NUFFT_FUSED": "0"}, "generic": {"CRIMP_NUFFT_ROWS4096": "0"}}
+            "generic": {"CRIMP_NUFFT_ROWS4096": "0"}}
+KNOBS = ("CRIMP_NUFFT_SPREAD", "CRIMP_NUFFT_LANES", "CRIMP_NUFFT_ROWS4096")
 print("plan", N.last_nufft_plan() if False else "", flush=True)
 for m in range(1, M + 1):
     row = []
     for v, env in variants.items():
-        for k in ("CRIMP_NUFFT_SPREAD", "CRIMP_NUFFT_LANES", "CRIMP_NUFFT_FUSED", "CRIMP_NUFFT_ROWS4096"):
+        for k in KNOBS:
             os.environ.pop(k, None)
         os.environ.update(env)
         z = ops.search(t, t0, f, m, 0, flags=N.FLAG_NO_FIXUP).cpu().numpy()[trial]
         row.append((v, z))
         if m == 1 and v == "auto":
             print("plan", N.last_nufft_plan(), flush=True)
-    for k in ("CRIMP_NUFFT_SPREAD", "CRIMP_NUFFT_LANES", "CRIMP_NUFFT_FUSED", "CRIMP_NUFFT_ROWS4096"):
+    for k in KNOBS:
         os.environ.pop(k, None)
     z64 = ops.search(t, t0, f, m, 0, precision="f64").cpu().numpy()[trial]
     zx = ops.search(t, t0, f, m, 0, precision="exact").cpu().numpy()[trial]
