@@ -1,7 +1,9 @@
 """``crimp`` import name for the MI355X build: ``from crimp.periodsearch import PeriodSearch`` and every other
 ``crimp.<module>`` of the photon hot path resolve to the drop-in module ``crimp_amd.<module>`` (the same module
 object, so state and classes are shared). Modules the build does not provide (plotting, timing-model fitting,
-SURVEY.md section 2 out of scope) raise ImportError as a missing module would."""
+SURVEY.md section 2 out of scope) raise ImportError as a missing module would. The pulse-profile plots are provided
+as ``crimp_amd.plot_pps`` (and the ``pulseprofile_plots`` script) only: the alias stays with the hot-path modules, as
+tests/test_capi_and_host.py::test_crimp_import_name_and_entry_points pins it (``crimp.plot_pps`` raises)."""
 import importlib
 import importlib.abc
 import importlib.util
@@ -9,12 +11,15 @@ import sys
 
 from crimp_amd import __version__  # noqa: F401
 
+NOT_ALIASED = ("plot_pps",)  # crimp_amd modules outside the hot path: imported under their own name only
+
 
 class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
     def find_spec(self, fullname, path, target=None):
         if not fullname.startswith("crimp.") or fullname.count(".") != 1:
             return None
-        if importlib.util.find_spec("crimp_amd." + fullname.split(".", 1)[1]) is None:
+        name = fullname.split(".", 1)[1]
+        if name in NOT_ALIASED or importlib.util.find_spec("crimp_amd." + name) is None:
             return None
         return importlib.util.spec_from_loader(fullname, self)
 

@@ -36,6 +36,14 @@ MAX_GLITCH = 32
 MAX_WAVE = 64
 MAX_COMP = 16
 
+CUBE_Y_OPEN_LAST = 1
+CUBE_Z_OPEN_LAST = 2
+CUBE_Y_IS_X = 4
+CUBE_PH_OPEN_LAST = 8
+CUBE_MAX_BINS = 1024
+CUBE_MAX_PH_EDGES = 2048
+CUBE_LDS_BINS = 4096
+
 
 class CrimpNativeError(RuntimeError):
     """Raised when the HIP library is unavailable or a native call fails."""
@@ -61,7 +69,7 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_last_search_path", "crimp_last_nufft_plan", "crimp_last_nufft_work", "crimp_last_toa_grid_norms", "crimp_last_toa_grid_fast", "crimp_release_scratch",
            "crimp_device_count", "crimp_calcphase", "crimp_search", "crimp_search_best", "crimp_best", "crimp_search_sets", "crimp_toa_points",
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
-           "crimp_is_sorted", "crimp_select_intervals", "crimp_gather_ranges")
+           "crimp_phase_cube", "crimp_is_sorted", "crimp_select_intervals", "crimp_gather_ranges")
 
 _lib = None
 _lock = threading.Lock()
@@ -101,6 +109,7 @@ def load(require_device=True):
             L.crimp_toa_fit.argtypes = [P, P, i64, ctypes.POINTER(Template), P, ctypes.c_double, i32, i32, P, u32, P]
             L.crimp_toa_shape_points.argtypes = [P, P, i64, ctypes.POINTER(Template), P, P, P, P, i64, P, u32, P]
             L.crimp_binphases.argtypes = [P, P, i64, P, i32, P, u32, P]
+            L.crimp_phase_cube.argtypes = [P, i64, ctypes.POINTER(TimingModel), P, P, i32, P, P, i32, P, P, P, i32, u32, P]
             L.crimp_is_sorted.argtypes = [P, i64, ctypes.POINTER(i32), u32, P]
             L.crimp_select_intervals.argtypes = [P, i64, P, P, i64, P, P, P, u32, P]
             L.crimp_gather_ranges.argtypes = [P, i64, P, P, i64, P, u32, P]

@@ -1484,6 +1484,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 
 #include "toa_fit.h"
 #include "toa_shape.h"
+#include "phase_cube.h"
 
 // ============================================================== 6. C-ABI
 static hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -1533,21 +1534,10 @@ static int finish(hipStream_t s, uint32_t flags) {
     return CRIMP_OK;
 }
 
-extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timing_model* model, int32_t parts,
-                               double* total, double* folded, uint32_t flags, void* stream) {
-    ARGCHK(n >= 0, "n < 0");
-    ARGCHK(model != nullptr && total != nullptr && (t_mjd != nullptr || n == 0), "null argument");
-    ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
-    ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
-    if (n == 0) return CRIMP_OK;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
-    CPModel hm{};
+// the kernels' form of a timing model (crimp_calcphase and the fused crimp_phase_cube share it, coefficient for
+// coefficient)
+static void make_cpmodel(const crimp_timing_model* model, int32_t parts, CPModel* out) {
+    CPModel& hm = *out;
     hm.pepoch = model->pepoch;
     hm.nterms = 0;
     double fact = 1.0;
@@ -1564,6 +1554,24 @@ extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timin
     hm.wave_om = model->wave_om;
     hm.f0 = model->f[0];
     std::memcpy(hm.wave_ab, model->wave_ab, sizeof(hm.wave_ab));
+}
+
+extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timing_model* model, int32_t parts,
+                               double* total, double* folded, uint32_t flags, void* stream) {
+    ARGCHK(n >= 0, "n < 0");
+    ARGCHK(model != nullptr && total != nullptr && (t_mjd != nullptr || n == 0), "null argument");
+    ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
+    ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+    if (n == 0) return CRIMP_OK;
+    std::lock_guard<std::mutex> lk(g_mutex);
+    if (flags & CRIMP_FLAG_TIME_KERNELS) {
+        g_kernel_times.clear();
+        g_last_kernel_ms = -1.0;
+    }
+    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
+    hipStream_t s = as_stream(stream);
+    CPModel hm{};
+    make_cpmodel(model, parts, &hm);
     {
         Scratch sc(s);
         const double* dt = nullptr;
@@ -3261,6 +3269,124 @@ extern "C" int crimp_binphases(const double* x, const int64_t* offsets, int64_t 
             dx, doff, de, nbins, reinterpret_cast<unsigned long long*>(dc));
         HIPCHK(hipGetLastError());
         HIPCHK(copy_back(s, counts, dc, (size_t)(nint * nbins), dev));
+    }
+    return finish(s, flags);
+}
+
+// edges[nb + 1] finite and strictly ascending (np.histogramdd's own demand)
+static bool cube_edges_ok(const double* e, int nb) {
+    for (int i = 0; i <= nb; ++i)
+        if (!std::isfinite(e[i]) || (i > 0 && !(e[i] > e[i - 1]))) return false;
+    return true;
+}
+
+extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_model* model, const double* y,
+                                const double* y_edges, int32_t ny, const double* z, const double* z_edges, int32_t nz,
+                                const double* ph_edges, const int32_t* nph, int64_t* counts, int32_t options,
+                                uint32_t flags, void* stream) {
+    ARGCHK(n >= 0 && n <= (int64_t(1) << 40), "n out of range");
+    ARGCHK(counts != nullptr && ph_edges != nullptr && nph != nullptr && (x != nullptr || n == 0), "null argument");
+    ARGCHK((options & ~(CRIMP_CUBE_Y_OPEN_LAST | CRIMP_CUBE_Z_OPEN_LAST | CRIMP_CUBE_Y_IS_X |
+                        CRIMP_CUBE_PH_OPEN_LAST)) == 0, "unknown option bits");
+    ARGCHK(ny >= 1 && ny <= CRIMP_CUBE_MAX_BINS && nz >= 1 && nz <= CRIMP_CUBE_MAX_BINS,
+           "ny and nz must be 1..CRIMP_CUBE_MAX_BINS");
+    const bool y_is_x = options & CRIMP_CUBE_Y_IS_X;
+    ARGCHK(!(y_is_x && y != nullptr), "CRIMP_CUBE_Y_IS_X takes y = NULL");
+    const bool has_y = y != nullptr || y_is_x, has_z = z != nullptr;
+    ARGCHK(has_y || ny == 1, "y == NULL is an axis of one bin: ny must be 1");
+    ARGCHK(has_z || nz == 1, "z == NULL is an axis of one bin: nz must be 1");
+    ARGCHK(!has_y || y_edges != nullptr, "y_edges missing");
+    ARGCHK(!has_z || z_edges != nullptr, "z_edges missing");
+    ARGCHK(!has_y || cube_edges_ok(y_edges, ny), "y_edges must be finite and strictly ascending");
+    ARGCHK(!has_z || cube_edges_ok(z_edges, nz), "z_edges must be finite and strictly ascending");
+    std::vector<int32_t> zoff((size_t)nz + 1, 0);
+    for (int j = 0; j < nz; ++j) {
+        ARGCHK(nph[j] >= 1 && nph[j] <= CRIMP_CUBE_MAX_BINS, "nph must be 1..CRIMP_CUBE_MAX_BINS");
+        zoff[(size_t)j + 1] = zoff[(size_t)j] + nph[j];
+        ARGCHK(zoff[(size_t)j + 1] + j + 1 <= CRIMP_CUBE_MAX_PH_EDGES, "more than CRIMP_CUBE_MAX_PH_EDGES phase edges");
+        ARGCHK(cube_edges_ok(ph_edges + zoff[(size_t)j] + j, nph[j]), "ph_edges must be finite and strictly ascending");
+    }
+    if (model != nullptr) {
+        ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
+        ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+    }
+    CubeDims D{};
+    D.ny = ny;
+    D.nz = nz;
+    D.has_y = has_y;
+    D.has_z = has_z;
+    D.y_is_x = y_is_x;
+    D.S = zoff[(size_t)nz];
+    D.cells = ny * D.S;
+    D.nph_edges = D.S + nz;
+    cube_copies(D.cells, &D.stride, &D.R);
+    D.open_y = (options & CRIMP_CUBE_Y_OPEN_LAST) != 0;
+    D.open_z = (options & CRIMP_CUBE_Z_OPEN_LAST) != 0;
+    D.open_p = (options & CRIMP_CUBE_PH_OPEN_LAST) != 0;
+    D.fused = model != nullptr;
+    // the lookup of every axis: estimate-and-step where the edges allow it (numpy.linspace's do), else a binary search
+    std::vector<double> psc((size_t)nz);
+    D.uni_y = has_y && cube_axis_uniform(y_edges, ny);
+    D.uni_z = has_z && cube_axis_uniform(z_edges, nz);
+    D.sc_y = has_y ? cube_axis_scale(y_edges, ny) : 0.0;
+    D.sc_z = has_z ? cube_axis_scale(z_edges, nz) : 0.0;
+    D.it_y = cube_search_steps(ny);
+    D.it_z = cube_search_steps(nz);
+    D.uni_p = 1;
+    D.it_p = 0;
+    for (int j = 0; j < nz; ++j) {
+        const double* e = ph_edges + zoff[(size_t)j] + j;
+        psc[(size_t)j] = cube_axis_scale(e, nph[j]);
+        D.uni_p = D.uni_p && cube_axis_uniform(e, nph[j]);
+        D.it_p = std::max(D.it_p, cube_search_steps(nph[j]));
+    }
+    std::lock_guard<std::mutex> lk(g_mutex);
+    if (flags & CRIMP_FLAG_TIME_KERNELS) {
+        g_kernel_times.clear();
+        g_last_kernel_ms = -1.0;
+    }
+    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
+    hipStream_t s = as_stream(stream);
+    CPModel hm{};
+    if (model) make_cpmodel(model, 7, &hm);
+    {
+        Scratch sc(s);
+        const double *dx = nullptr, *dy = nullptr, *dz = nullptr;
+        int64_t* dc = nullptr;
+        HIPCHK(stage_out(sc, counts, (size_t)D.cells, dev, &dc));
+        HIPCHK(hipMemsetAsync(dc, 0, (size_t)D.cells * sizeof(int64_t), s));
+        if (n > 0) {
+            HIPCHK(stage_in(sc, x, (size_t)n, dev, &dx));
+            HIPCHK(stage_in(sc, y, (size_t)n, dev, &dy));
+            HIPCHK(stage_in(sc, z, (size_t)n, dev, &dz));
+            // the edge tables in the kernel's LDS order, and the column offsets: one small upload each
+            std::vector<double> tab;
+            if (has_y) tab.insert(tab.end(), y_edges, y_edges + ny + 1);
+            if (has_z) tab.insert(tab.end(), z_edges, z_edges + nz + 1);
+            tab.insert(tab.end(), ph_edges, ph_edges + D.nph_edges);
+            tab.insert(tab.end(), psc.begin(), psc.end());
+            double* dtab = nullptr;
+            int32_t* dzoff = nullptr;
+            HIPCHK(sc.alloc(&dtab, tab.size()));
+            HIPCHK(sc.alloc(&dzoff, zoff.size()));
+            pin_begin((tab.size() * sizeof(double) + 255 + zoff.size() * sizeof(int32_t) + 255));
+            HIPCHK(h2d_async(s, dtab, tab.data(), tab.size() * sizeof(double)));
+            HIPCHK(h2d_async(s, dzoff, zoff.data(), zoff.size() * sizeof(int32_t)));
+            const bool vec = ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(dy) |
+                               reinterpret_cast<uintptr_t>(dz)) & 15u) == 0;
+            const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(vec ? n / 2 : n, kCubeBlock),
+                                                                             kCubeMaxBlocks));
+            const size_t lds = cube_lds_bytes(D);
+            KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+            kt.start();
+            auto kern = vec ? (cube_is_map(D) ? k_phase_cube<true, true> : k_phase_cube<true, false>)
+                            : (cube_is_map(D) ? k_phase_cube<false, true> : k_phase_cube<false, false>);
+            kern<<<blocks, kCubeBlock, lds, s>>>(dx, dy, dz, n, hm, dtab, dzoff, D,
+                                                 reinterpret_cast<unsigned long long*>(dc));
+            HIPCHK(hipGetLastError());
+            kt.stop();
+        }
+        HIPCHK(copy_back(s, counts, dc, (size_t)D.cells, dev));
     }
     return finish(s, flags);
 }

@@ -343,6 +343,62 @@ def binphases_counts(x, offsets, edges):
     return out.reshape(nint, nb)
 
 
+def phase_cube(x, model=None, y=None, y_edges=None, z=None, z_edges=None, ph_edges=None, nph=None, options=0,
+               flags=0):
+    """The (y, z, phase) count cube of crimp_phase_cube: int64 [ny, S], S = sum of the z columns' phase bins (column j
+    is [:, zoff[j] : zoff[j + 1]], zoff the prefix sum of the bin counts), a NumPy array for host inputs and a tensor
+    on the photons' GPU for device tensors.
+
+    ``x``: folded phases, or -- with ``model`` (a timing-model dict) -- MJD times folded on the device in the same pass
+    (calcphase's folded phase, exactly). ``y`` / ``z`` with ``y_edges`` / ``z_edges``: the two other axes (None: one
+    bin that takes every photon); option ``N.CUBE_Y_IS_X``: y = x, given as ``y_edges`` alone. Phase axis:
+    ``ph_edges`` -- one edge array, or one per z column -- or ``nph`` -- a bin count, or one per z column, over
+    numpy.linspace(0, 1, n + 1). Every axis bins as np.histogramdd with explicit edges; ``options``
+    N.CUBE_Y_OPEN_LAST / CUBE_Z_OPEN_LAST / CUBE_PH_OPEN_LAST drop a value equal to that axis's last edge. The edges
+    are host data always."""
+    L = N.load()
+    b = N.Buffers()
+    xp = b.arg(x, np.float64)
+    n = int(x.numel() if N._is_torch(x) else np.size(x))
+    yp = b.arg(y, np.float64, allow_none=True)
+    zp = b.arg(z, np.float64, allow_none=True)
+    for a in (y, z):
+        if a is not None and int(a.numel() if N._is_torch(a) else np.size(a)) != n:
+            raise ValueError("x, y and z differ in length")
+
+    def host(e):
+        return None if e is None else np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+    ye, ze = host(y_edges), host(z_edges)
+    ny = 1 if ye is None else ye.size - 1
+    nz = 1 if ze is None else ze.size - 1
+    if ph_edges is None:
+        if nph is None:
+            raise ValueError("phase_cube needs ph_edges or nph")
+        bins = [int(nph)] * nz if np.isscalar(nph) else [int(v) for v in nph]
+        cols = [np.linspace(0, 1, k + 1) for k in bins]
+    elif isinstance(ph_edges, (list, tuple)) and len(ph_edges) and np.ndim(ph_edges[0]) == 1:
+        cols = [host(e) for e in ph_edges]
+    else:
+        cols = [host(ph_edges)] * nz
+    if len(cols) != nz:
+        raise ValueError("one phase-edge array (or bin count) per z column: %d for %d columns" % (len(cols), nz))
+    if min(c.size for c in cols) < 2 or ny < 1 or nz < 1:
+        raise ValueError("an axis needs at least two edges")
+    nphs = np.array([c.size - 1 for c in cols], dtype=np.int32)
+    pe = np.ascontiguousarray(np.concatenate(cols))
+    S = int(nphs.sum())
+    out = _empty_like_input(x, ny * S, b, dtype=np.int64)
+    cp = b.arg(out, np.int64, writable=True)
+    m = None if model is None else ctypes.byref(_modeltm(model))
+
+    def ptr(a):
+        return None if a is None else ctypes.c_void_p(a.ctypes.data)
+    with b.device_guard():
+        N.check(L.crimp_phase_cube(xp, n, m, yp, ptr(ye), ny, zp, ptr(ze), nz, ptr(pe), ptr(nphs), cp, int(options),
+                                   b.flags(flags), b.stream()))
+    return out.reshape(ny, S)
+
+
 def is_sorted(t):
     """True when the times are non-decreasing (crimp_is_sorted; a NaN counts as out of order), as
     np.all(t[1:] >= t[:-1])."""

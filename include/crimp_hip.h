@@ -253,6 +253,36 @@ int crimp_toa_fit_redchi2(const double* x, const int64_t* offsets, int64_t nint,
 int crimp_binphases(const double* x, const int64_t* offsets, int64_t nint, const double* edges, int32_t nbins,
                     int64_t* counts, uint32_t flags, void* stream);
 
+/* The count cube behind the pulse-profile maps of plot_pps.py: np.histogram2d(phases, energies | times, bins=[...])
+ * (:149, :214), the per-tile binphases of the time x energy grid (:319-333) and of the before / after windows
+ * (:469-477), folding and binning in one pass when a timing model is given (not in the reference: calcphase, then
+ * the histogram on its output).
+ *   x[n]: folded phases (model == NULL; cycles or radians, the phase edges decide), or MJD times (model != NULL)
+ *         whose phase is calcphase's `folded` (parts = 7, cycles), formed exactly as crimp_calcphase forms it: a fused
+ *         call gives the counts of crimp_calcphase followed by an unfused call.
+ *   y[n] with y_edges[ny + 1], z[n] with z_edges[nz + 1]: the two other axes. A NULL y (z) is an axis of one bin that
+ *         takes every photon: ny (nz) must be 1, the edges are ignored. CRIMP_CUBE_Y_IS_X: y = x (y must be NULL).
+ *   nph[nz]: phase bins of every z column (plotting_pp_grid's nbrbins, :277); ph_edges: the columns' nph[j] + 1 edges
+ *         concatenated (sum of nph[j] + 1 <= CRIMP_CUBE_MAX_PH_EDGES).
+ *   counts[iy * S + zoff[iz] + b], zoff = prefix sum of nph, S = zoff[nz]; int64, zeroed by the call.
+ * Bin rule of every axis (np.histogramdd with explicit edges): bin = np.searchsorted(edges, v, 'right') - 1; v equal
+ * to the last edge counts in the last bin unless the axis's OPEN_LAST option is set; a value outside the edges or a NaN
+ * drops the photon. Exact comparisons against the edges as passed; edges strictly ascending and finite
+ * (else CRIMP_ERR_ARG). The edges, nph and the model are host pointers always; x, y, z and counts follow
+ * CRIMP_FLAG_DEVICE_PTRS. CRIMP_FLAG_TIME_KERNELS times the kernel (crimp_last_kernel_ms). n == 0 gives zeros. */
+#define CRIMP_CUBE_Y_OPEN_LAST 1  /* y axis: last bin [e, e') like the others (plot_pps.py:325), not numpy's closed last bin */
+#define CRIMP_CUBE_Z_OPEN_LAST 2  /* the same for the z axis */
+#define CRIMP_CUBE_Y_IS_X      4  /* y = x (time axis of a fused phase-time map): x is read once */
+#define CRIMP_CUBE_PH_OPEN_LAST 8 /* the same for the phase axis: a phase equal to the last edge is dropped */
+#define CRIMP_CUBE_MAX_BINS 1024  /* per axis */
+#define CRIMP_CUBE_MAX_PH_EDGES 2048 /* phase edges of all z columns together */
+#define CRIMP_CUBE_LDS_BINS 4096  /* largest cube (cells) counted in LDS; above it, global atomics */
+int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_model* model,
+                     const double* y, const double* y_edges, int32_t ny,
+                     const double* z, const double* z_edges, int32_t nz,
+                     const double* ph_edges, const int32_t* nph,
+                     int64_t* counts, int32_t options, uint32_t flags, void* stream);
+
 /* Interval selection of measureToAs (measureToAs.py:168-182): TIME[(TIME >= start) & (TIME <= end)] per ToA interval
  * (:173-174) and its first / last photon (ToA_mid, :182).
  * crimp_is_sorted: *unsorted = 1 if some t[i+1] < t[i] (or a NaN), else 0 (host int; t host or device per flags).
