@@ -1,8 +1,10 @@
 """``crimp`` import name for the MI355X build: ``from crimp.periodsearch import PeriodSearch`` and every other
-``crimp.<module>`` of the photon hot path resolve to the drop-in module ``crimp_amd.<module>`` (the same module
-object, so state and classes are shared). Modules the build does not provide (plotting, timing-model fitting,
-SURVEY.md section 2 out of scope) raise ImportError as a missing module would. The pulse-profile plots are provided
-as ``crimp_amd.plot_pps`` (and the ``pulseprofile_plots`` script) only: the alias stays with the hot-path modules, as
+``crimp.<module>`` this build provides resolve to the drop-in module ``crimp_amd.<module>`` (the same module object,
+so state and classes are shared): the photon hot path (``calcphase``, ``periodsearch``, ``templatemodels``,
+``measureToAs``, ``pulseprofile``, ``eventfile``, ``timfile``, ...) and the timing-model fits of the ToAs
+(``fit_toas``, ``utilities_fittoas``, ``get_local_ephem``, ``plot_local_ephem``). Modules the build does not provide
+(``diagnoseToAs``, ``merge_overlapping_timfiles``, the simulator) raise ImportError as a missing module would. The
+pulse-profile plots are provided as ``crimp_amd.plot_pps`` (and the ``pulseprofile_plots`` script) only, as
 tests/test_capi_and_host.py::test_crimp_import_name_and_entry_points pins it (``crimp.plot_pps`` raises)."""
 import importlib
 import importlib.abc
@@ -11,7 +13,7 @@ import sys
 
 from crimp_amd import __version__  # noqa: F401
 
-NOT_ALIASED = ("plot_pps",)  # crimp_amd modules outside the hot path: imported under their own name only
+NOT_ALIASED = ("plot_pps",)  # imported under its own name only
 
 
 class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):

@@ -58,6 +58,19 @@ class TimingModel(ctypes.Structure):
 
 SHAPE_SUMS = 4 + 3 * MAX_COMP  # CRIMP_SHAPE_SUMS
 
+FIT_MAX_DIM = 32
+FIT_WAVES_FIXED, FIT_WAVES_ONLY, FIT_WAVES_MIXED = 0, 1, 2
+FIT_SLOT_F, FIT_SLOT_GLITCH, FIT_SLOT_WAVE = 0, 1, 2
+
+
+class FitSlot(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("index", ctypes.c_int32), ("sub", ctypes.c_int32)]
+
+
+class FitMap(ctypes.Structure):
+    _fields_ = [("ndim", ctypes.c_int32), ("branch", ctypes.c_int32), ("f0_param", ctypes.c_int32),
+                ("slot", FitSlot * FIT_MAX_DIM)]
+
 
 class Template(ctypes.Structure):
     _fields_ = [("model", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("amp", ctypes.c_double * MAX_COMP),
@@ -69,7 +82,8 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_last_search_path", "crimp_last_nufft_plan", "crimp_last_nufft_work", "crimp_last_toa_grid_norms", "crimp_last_toa_grid_fast", "crimp_release_scratch",
            "crimp_device_count", "crimp_calcphase", "crimp_search", "crimp_search_best", "crimp_best", "crimp_search_sets", "crimp_toa_points",
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
-           "crimp_phase_cube", "crimp_is_sorted", "crimp_select_intervals", "crimp_gather_ranges")
+           "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
+           "crimp_gather_ranges")
 
 _lib = None
 _lock = threading.Lock()
@@ -110,6 +124,10 @@ def load(require_device=True):
             L.crimp_toa_shape_points.argtypes = [P, P, i64, ctypes.POINTER(Template), P, P, P, P, i64, P, u32, P]
             L.crimp_binphases.argtypes = [P, P, i64, P, i32, P, u32, P]
             L.crimp_phase_cube.argtypes = [P, i64, ctypes.POINTER(TimingModel), P, P, i32, P, P, i32, P, P, P, i32, u32, P]
+            MP, FP = ctypes.POINTER(TimingModel), ctypes.POINTER(FitMap)
+            L.crimp_timing_nll.argtypes = [P, P, P, P, i64, MP, MP, FP, P, i64, P, P, u32, P]
+            L.crimp_timing_mcmc.argtypes = [P, P, P, P, i64, MP, MP, FP, P, P, P, i32, i64, ctypes.c_uint64, i64, P, P, P,
+                                            u32, P]
             L.crimp_is_sorted.argtypes = [P, i64, ctypes.POINTER(i32), u32, P]
             L.crimp_select_intervals.argtypes = [P, i64, P, P, i64, P, P, P, u32, P]
             L.crimp_gather_ranges.argtypes = [P, i64, P, P, i64, P, u32, P]

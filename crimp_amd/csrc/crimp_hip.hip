@@ -1485,6 +1485,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "toa_fit.h"
 #include "toa_shape.h"
 #include "phase_cube.h"
+#include "timing_fit.h"
 
 // ============================================================== 6. C-ABI
 static hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -3390,6 +3391,212 @@ extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_m
     }
     return finish(s, flags);
 }
+
+// ---- timing-model fits of ToAs (timing_fit.h)
+// the kernels' form of the per-problem models and of the map, with every check of crimp_timing_nll / _mcmc on them
+static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_model* fit_base,
+                      const crimp_timing_model* wave_base, const crimp_fit_map* map, std::vector<TFModel>* models,
+                      TFMap* dm) {
+    ARGCHK(nprob >= 1 && nprob <= (int64_t(1) << 24), "nprob out of range");
+    ARGCHK(fit_base != nullptr && wave_base != nullptr && map != nullptr, "null argument");
+    ARGCHK(map->ndim >= 1 && map->ndim <= CRIMP_FIT_MAX_DIM, "ndim must be 1..CRIMP_FIT_MAX_DIM");
+    ARGCHK(map->branch >= CRIMP_FIT_WAVES_FIXED && map->branch <= CRIMP_FIT_WAVES_MIXED, "unknown branch");
+    ARGCHK(map->f0_param >= -1 && map->f0_param < map->ndim, "f0_param out of range");
+    *dm = TFMap{};
+    dm->ndim = map->ndim;
+    dm->f0_param = map->f0_param;
+    double fact = 1.0;
+    for (int k = 0; k < 13; ++k) {
+        fact *= (double)(k + 1);
+        dm->inv_fact[k] = 1.0 / fact;
+    }
+    int top_f = 0, top_gl = -1, top_wv = -1;
+    for (int k = 0; k < map->ndim; ++k) {
+        const crimp_fit_slot& sl = map->slot[k];
+        if (sl.kind == CRIMP_FIT_SLOT_F) {
+            ARGCHK(sl.index >= 0 && sl.index <= 12, "slot names an F term outside F0..F12");
+            top_f = std::max(top_f, sl.index + 1);
+        } else if (sl.kind == CRIMP_FIT_SLOT_GLITCH) {
+            ARGCHK(sl.index >= 0 && sl.index < CRIMP_MAX_GLITCH && sl.sub >= 0 && sl.sub <= 6,
+                   "slot names a glitch field outside the model");
+            top_gl = std::max(top_gl, sl.index);
+        } else if (sl.kind == CRIMP_FIT_SLOT_WAVE) {
+            ARGCHK(sl.index >= 0 && sl.index < CRIMP_MAX_WAVE && sl.sub >= 0 && sl.sub <= 1,
+                   "slot names a wave field outside the model");
+            ARGCHK(map->branch != CRIMP_FIT_WAVES_FIXED, "a wave slot with CRIMP_FIT_WAVES_FIXED");
+            top_wv = std::max(top_wv, sl.index);
+        } else {
+            return set_err(CRIMP_ERR_ARG, "unknown slot kind");
+        }
+        ARGCHK(k != map->f0_param || (sl.kind == CRIMP_FIT_SLOT_F && sl.index == 0), "f0_param is not an F0 slot");
+        dm->kind[k] = sl.kind;
+        dm->a[k] = sl.index;
+        dm->b[k] = sl.kind == CRIMP_FIT_SLOT_F ? 0 : sl.sub;
+    }
+    models->resize((size_t)nprob);
+    for (int64_t i = 0; i < nprob; ++i) {
+        const crimp_timing_model &fm = fit_base[i], &wm = wave_base[i];
+        ARGCHK(h_off[i + 1] > h_off[i], "a problem has no ToAs");
+        ARGCHK(h_off[i + 1] - h_off[i] <= (int64_t(1) << 30), "a problem has too many ToAs");
+        ARGCHK(fm.n_glitch >= 0 && fm.n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
+        ARGCHK(fm.n_wave >= 0 && fm.n_wave <= CRIMP_MAX_WAVE && wm.n_wave >= 0 && wm.n_wave <= CRIMP_MAX_WAVE,
+               "n_wave out of range");
+        ARGCHK(top_gl < fm.n_glitch, "slot names a glitch outside the model");
+        ARGCHK(top_wv < fm.n_wave, "slot names a wave harmonic outside the model");
+        TFModel& tm = (*models)[(size_t)i];
+        make_cpmodel(&fm, map->branch == CRIMP_FIT_WAVES_ONLY ? 4 : 7, &tm.m);
+        tm.m.nterms = std::max(tm.m.nterms, top_f);
+        if (map->branch == CRIMP_FIT_WAVES_FIXED) {  // utilities_fittoas.py:283: the full model's waves
+            tm.m.n_wave = wm.n_wave;
+            tm.m.wave_epoch = wm.wave_epoch;
+            tm.m.wave_om = wm.wave_om;
+            std::memcpy(tm.m.wave_ab, wm.wave_ab, sizeof(tm.m.wave_ab));
+        }
+        tm.f0_base = wm.f[0];
+        tm.m.f0 = wm.f[0];
+    }
+    return CRIMP_OK;
+}
+
+// offsets on the host (the checks and the LDS plan need the ToA counts)
+static int tf_host_offsets(const int64_t* offsets, int64_t nprob, bool dev, hipStream_t s, std::vector<int64_t>* h) {
+    ARGCHK(offsets != nullptr && nprob >= 1 && nprob <= (int64_t(1) << 24), "nprob out of range");
+    h->resize((size_t)nprob + 1);
+    if (dev) {
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipMemcpy(h->data(), offsets, h->size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    } else {
+        std::memcpy(h->data(), offsets, h->size() * sizeof(int64_t));
+    }
+    ARGCHK((*h)[0] == 0, "offsets[0] must be 0");
+    return CRIMP_OK;
+}
+
+extern "C" int crimp_timing_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                                int64_t nprob, const crimp_timing_model* fit_base,
+                                const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec,
+                                int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
+    ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && pvec != nullptr && nll != nullptr, "null argument");
+    ARGCHK(P >= 1 && P <= (int64_t(1) << 24), "P out of range");
+    std::lock_guard<std::mutex> lk(g_mutex);
+    if (flags & CRIMP_FLAG_TIME_KERNELS) {
+        g_kernel_times.clear();
+        g_last_kernel_ms = -1.0;
+    }
+    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
+    hipStream_t s = as_stream(stream);
+    std::vector<int64_t> h_off;
+    std::vector<TFModel> models;
+    TFMap dm;
+    int rc = tf_host_offsets(offsets, nprob, dev, s, &h_off);
+    if (rc != CRIMP_OK) return rc;
+    rc = tf_prepare(h_off.data(), nprob, fit_base, wave_base, map, &models, &dm);
+    if (rc != CRIMP_OK) return rc;
+    const int64_t groups = cdiv(P, kTfNllWaves);
+    ARGCHK(nprob * groups <= (int64_t(1) << 30), "too many parameter vectors for one launch");
+    const size_t ntoa = (size_t)h_off[(size_t)nprob], nd = (size_t)dm.ndim;
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp = nullptr;
+        const int64_t* doff = nullptr;
+        double *dnll = nullptr, *dmu = nullptr;
+        TFModel* dmod = nullptr;
+        TFMap* dmap = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
+        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
+        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
+        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
+        HIPCHK(stage_in(sc, pvec, (size_t)nprob * (size_t)P * nd, dev, &dp));
+        HIPCHK(stage_out(sc, nll, (size_t)nprob * (size_t)P, dev, &dnll));
+        HIPCHK(stage_out(sc, mu, (size_t)P * ntoa, dev, &dmu));
+        HIPCHK(sc.alloc(&dmod, models.size()));
+        HIPCHK(sc.alloc(&dmap, 1));
+        HIPCHK(h2d(dmod, models.data(), models.size() * sizeof(TFModel)));
+        HIPCHK(h2d(dmap, &dm, sizeof(TFMap)));
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        k_timing_nll<<<(unsigned)(nprob * groups), kTfNllWaves * 64, 0, s>>>(dt, dy, de, doff, dmod, dmap, dp, P, groups,
+                                                                             dnll, dmu);
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, nll, dnll, (size_t)nprob * (size_t)P, dev));
+        HIPCHK(copy_back(s, mu, dmu, (size_t)P * ntoa, dev));
+    }
+    return finish(s, flags);
+}
+
+extern "C" int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                                 int64_t nprob, const crimp_timing_model* fit_base,
+                                 const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
+                                 const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                                 int64_t first_problem, double* chain, double* logprob, int64_t* accepted,
+                                 uint32_t flags, void* stream) {
+    ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && p0 != nullptr && lo != nullptr && hi != nullptr &&
+               chain != nullptr && logprob != nullptr && accepted != nullptr, "null argument");
+    ARGCHK(map != nullptr && map->ndim >= 1 && map->ndim <= CRIMP_FIT_MAX_DIM, "ndim must be 1..CRIMP_FIT_MAX_DIM");
+    ARGCHK(W >= 2 && W % 2 == 0 && W <= 256 && W >= 2 * map->ndim, "walkers: even, >= 2 ndim and <= 256");
+    ARGCHK(steps >= 1 && steps <= (int64_t(1) << 31), "steps out of range");
+    ARGCHK(first_problem >= 0 && first_problem + nprob <= (int64_t(1) << 32), "first_problem out of range");
+    std::lock_guard<std::mutex> lk(g_mutex);
+    if (flags & CRIMP_FLAG_TIME_KERNELS) {
+        g_kernel_times.clear();
+        g_last_kernel_ms = -1.0;
+    }
+    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
+    hipStream_t s = as_stream(stream);
+    std::vector<int64_t> h_off;
+    std::vector<TFModel> models;
+    TFMap dm;
+    int rc = tf_host_offsets(offsets, nprob, dev, s, &h_off);
+    if (rc != CRIMP_OK) return rc;
+    rc = tf_prepare(h_off.data(), nprob, fit_base, wave_base, map, &models, &dm);
+    if (rc != CRIMP_OK) return rc;
+    const size_t ntoa = (size_t)h_off[(size_t)nprob], nd = (size_t)dm.ndim, w = (size_t)W;
+    int64_t nmax = 0;
+    for (int64_t i = 0; i < nprob; ++i) nmax = std::max(nmax, h_off[(size_t)i + 1] - h_off[(size_t)i]);
+    // LDS: positions, log-probabilities, counts, one model per wave; the ToAs too when the largest problem's fit
+    constexpr size_t kLdsCap = 128 * 1024;
+    size_t lds = (w * nd + 2 * w) * sizeof(double) + kTfMcWaves * sizeof(CPModel);
+    const int stage = lds + 3 * (size_t)nmax * sizeof(double) <= kLdsCap;
+    if (stage) lds += 3 * (size_t)nmax * sizeof(double);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_timing_mcmc), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kLdsCap));
+    const size_t rows = (size_t)nprob * (size_t)steps * w;
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp0 = nullptr, *dlo = nullptr, *dhi = nullptr;
+        const int64_t* doff = nullptr;
+        double *dchain = nullptr, *dlp = nullptr;
+        int64_t* dacc = nullptr;
+        TFModel* dmod = nullptr;
+        TFMap* dmap = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
+        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
+        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
+        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
+        HIPCHK(stage_in(sc, p0, (size_t)nprob * w * nd, dev, &dp0));
+        HIPCHK(stage_in(sc, lo, (size_t)nprob * nd, dev, &dlo));
+        HIPCHK(stage_in(sc, hi, (size_t)nprob * nd, dev, &dhi));
+        HIPCHK(stage_out(sc, chain, rows * nd, dev, &dchain));
+        HIPCHK(stage_out(sc, logprob, rows, dev, &dlp));
+        HIPCHK(stage_out(sc, accepted, (size_t)nprob * w, dev, &dacc));
+        HIPCHK(sc.alloc(&dmod, models.size()));
+        HIPCHK(sc.alloc(&dmap, 1));
+        HIPCHK(h2d(dmod, models.data(), models.size() * sizeof(TFModel)));
+        HIPCHK(h2d(dmap, &dm, sizeof(TFMap)));
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        k_timing_mcmc<<<(unsigned)nprob, kTfMcWaves * 64, lds, s>>>(dt, dy, de, doff, dmod, dmap, dp0, dlo, dhi, (int)W,
+                                                                    steps, seed, first_problem, stage, dchain, dlp, dacc);
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, chain, dchain, rows * nd, dev));
+        HIPCHK(copy_back(s, logprob, dlp, rows, dev));
+        HIPCHK(copy_back(s, accepted, dacc, (size_t)nprob * w, dev));
+    }
+    return finish(s, flags);
+}
+
 
 // ============================================================== 7. interval selection (measureToAs.py:168-182)
 // The photons of a ToA interval are TIME[(TIME >= start) & (TIME <= end)] (measureToAs.py:173-174); on time-sorted

@@ -399,6 +399,115 @@ def phase_cube(x, model=None, y=None, y_edges=None, z=None, z_edges=None, ph_edg
     return out.reshape(ny, S)
 
 
+_GLITCH_FIELDS = ("GLEP", "GLPH", "GLF0", "GLF1", "GLF2", "GLF0D", "GLTD")
+
+
+def fit_map(keys):
+    """crimp_fit_map of a list of free-parameter names (utilities_fittoas.list_fit_keys): the model field every
+    parameter overwrites and the branch of model_phase_residuals (utilities_fittoas.py:275-291) the names select."""
+    import re
+    if not 1 <= len(keys) <= N.FIT_MAX_DIM:
+        raise ValueError("a fit needs 1..%d free parameters, got %d" % (N.FIT_MAX_DIM, len(keys)))
+    m = N.FitMap()
+    m.ndim = len(keys)
+    m.f0_param = -1
+    wave = ["wave" in k.lower() for k in keys]
+    m.branch = N.FIT_WAVES_ONLY if all(wave) else N.FIT_WAVES_MIXED if any(wave) else N.FIT_WAVES_FIXED
+    for i, k in enumerate(keys):
+        f = re.match(r"^F(\d+)$", k)
+        g = re.match(r"^(GL[A-Z0-9]+)_(\d+)$", k)
+        w = re.match(r"^WAVE(\d+)_([AB])$", k)
+        if f:
+            slot = (N.FIT_SLOT_F, int(f.group(1)), 0)
+            if slot[1] == 0:
+                m.f0_param = i
+        elif g and g.group(1) in _GLITCH_FIELDS:
+            slot = (N.FIT_SLOT_GLITCH, int(g.group(2)) - 1, _GLITCH_FIELDS.index(g.group(1)))
+        elif w:
+            slot = (N.FIT_SLOT_WAVE, int(w.group(1)) - 1, "AB".index(w.group(2)))
+        else:
+            raise ValueError("parameter %r cannot be fitted (F0..F12, GL*_j and WAVEj_A/B can)" % k)
+        m.slot[i].kind, m.slot[i].index, m.slot[i].sub = slot
+    return m
+
+
+def _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases):
+    if isinstance(fit_bases, N.TimingModel):
+        fit_bases, wave_bases = [fit_bases], [wave_bases]
+    nprob = len(fit_bases)
+    if len(wave_bases) != nprob:
+        raise ValueError("one fit base and one wave base per problem")
+    if offsets is None:
+        n = int(t.numel() if N._is_torch(t) else np.size(t))
+        offsets = np.array([0, n], dtype=np.int64)
+        if N._is_torch(t) and t.is_cuda:
+            import torch
+            offsets = torch.as_tensor(offsets, device=t.device)
+    if int((offsets.numel() if N._is_torch(offsets) else np.size(offsets)) - 1) != nprob:
+        raise ValueError("offsets needs one entry more than there are problems")
+    ptrs = (b.arg(t, np.float64), b.arg(y, np.float64), b.arg(yerr, np.float64), b.arg(offsets, np.int64))
+    ntoa = int(t.numel() if N._is_torch(t) else np.size(t))
+    return ptrs, nprob, ntoa, (N.TimingModel * nprob)(*fit_bases), (N.TimingModel * nprob)(*wave_bases)
+
+
+def timing_nll(t, y, yerr, fit_bases, wave_bases, fmap, pvec, offsets=None, want_mu=False, flags=0):
+    """Gaussian NLL of the phase residuals for nprob problems x P parameter vectors in one launch (crimp_timing_nll).
+    ``t, y, yerr``: the ToAs of all problems concatenated, problem i = [offsets[i], offsets[i+1]) (offsets None: one
+    problem); ``fit_bases`` / ``wave_bases``: one N.TimingModel each per problem (or a single one);
+    ``pvec`` [nprob, P, ndim]. Returns nll [nprob, P], or (nll, mu) with ``want_mu``: mu flat, problem i's
+    mean-subtracted model residuals at mu[P * offsets[i]:] as [P, n_i]."""
+    L = N.load()
+    b = N.Buffers()
+    (tp, yp, ep, op), nprob, ntoa, fb, wb = _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases)
+    nd = int(fmap.ndim)
+    tot = int(pvec.numel() if N._is_torch(pvec) else np.size(pvec))
+    if nd < 1 or tot == 0 or tot % (nprob * nd):
+        raise ValueError("pvec must be [nprob, P, ndim]")
+    P = tot // (nprob * nd)
+    pp = b.arg(pvec, np.float64)
+    nll = _empty_like_input(t, nprob * P, b)
+    mu = _empty_like_input(t, P * ntoa, b) if want_mu else None
+    nllp = b.arg(nll, np.float64, writable=True)
+    mup = b.arg(mu, np.float64, writable=True) if want_mu else None
+    with b.device_guard():
+        N.check(L.crimp_timing_nll(tp, yp, ep, op, nprob, fb, wb, ctypes.byref(fmap), pp, P, nllp, mup,
+                                   b.flags(flags), b.stream()))
+    nll = nll.reshape(nprob, P)
+    return (nll, mu) if want_mu else nll
+
+
+def timing_mcmc(t, y, yerr, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets=None, first_problem=0,
+                flags=0):
+    """The ensemble sampler of nprob problems in one launch (crimp_timing_mcmc): ``p0`` [nprob, W, ndim], ``lo`` /
+    ``hi`` [nprob, ndim] (+-inf: no bound). Returns (chain [nprob, steps, W, ndim], logprob [nprob, steps, W],
+    accepted [nprob, W]); placement follows ``t``. Problem i draws the random stream of global index
+    ``first_problem + i``."""
+    L = N.load()
+    b = N.Buffers()
+    (tp, yp, ep, op), nprob, ntoa, fb, wb = _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases)
+    nd = int(fmap.ndim)
+    shape = tuple(p0.shape)
+    if len(shape) != 3 or shape[0] != nprob or shape[2] != nd:
+        raise ValueError("p0 must be [nprob, W, ndim]")
+    W, steps = int(shape[1]), int(steps)
+    for a in (lo, hi):
+        if int(a.numel() if N._is_torch(a) else np.size(a)) != nprob * nd:
+            raise ValueError("lo and hi must be [nprob, ndim]")
+    pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
+    rows = nprob * max(steps, 0) * W
+    chain = _empty_like_input(t, rows * nd, b)
+    logprob = _empty_like_input(t, rows, b)
+    accepted = _empty_like_input(t, nprob * W, b, dtype=np.int64)
+    cp = b.arg(chain, np.float64, writable=True)
+    lpp = b.arg(logprob, np.float64, writable=True)
+    ap = b.arg(accepted, np.int64, writable=True)
+    with b.device_guard():
+        N.check(L.crimp_timing_mcmc(tp, yp, ep, op, nprob, fb, wb, ctypes.byref(fmap), pp, lop, hip_, W, steps,
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_problem), cp, lpp, ap, b.flags(flags),
+                                    b.stream()))
+    return chain.reshape(nprob, steps, W, nd), logprob.reshape(nprob, steps, W), accepted.reshape(nprob, W)
+
+
 def is_sorted(t):
     """True when the times are non-decreasing (crimp_is_sorted; a NaN counts as out of order), as
     np.all(t[1:] >= t[:-1])."""

@@ -157,3 +157,116 @@ def get_parameter_value(entry):
     if isinstance(entry, dict) and {"value", "flag"} <= set(entry.keys()):
         return entry.get("value")
     return entry
+
+
+def add_pntrack_parfile(pardict, parfile):
+    """Add TRACK (-2: pulse numbering) of the .par file ``parfile`` to ``pardict``, in the dictionary's own style:
+    a {value, flag} entry if its entries are dicts, the plain value otherwise (readtimingmodel.py:324-332)."""
+    track = ReadTimingModel(parfile).readmiscellaneous().get("TRACK")
+    if track == -2:
+        nested = bool(pardict) and isinstance(next(iter(pardict.values())), dict)
+        pardict["TRACK"] = {"value": track, "flag": 0} if nested else track
+
+
+_NUMBER = r"[+-]?(?:\d+(?:\.\d*)?|\.\d+)(?:[eE][+-]?\d+)?"
+# KEY <ws> value [<ws> flag(0|1)] [<ws> uncertainty] tail
+_PAR_LINE = re.compile(r"^([A-Za-z][A-Za-z0-9_]*)(\s+)(\S+)(?:(\s+)([01]))?(?:\s+(" + _NUMBER + r"))?(.*)$")
+_PAR_WAVE_LINE = re.compile(r"^(WAVE\d+)\s+(\S+)\s+(\S+)(?:\s+.*)?$")
+
+
+def patch_par_values(in_path: str, out_path: str, *, new_values: dict, float_fmt: str = ".15g",
+                     uncertainties=None, uncertainty_fmt: str = ".6g") -> None:
+    """Rewrite the values of a .par file (readtimingmodel.py:335-432). Lines whose key is in ``new_values`` (plain
+    values or {value, flag} entries; WAVEj as {A, B}) get the new value in ``float_fmt``, keeping their spacing, fit
+    flag and tail; a flagged line also gets ``uncertainties[key]`` (or keeps the uncertainty it had). A WAVEj line is
+    rewritten as ``WAVEj A B``. Every other line passes through unchanged."""
+    def plain(v):
+        return v["value"] if isinstance(v, dict) and "value" in v else v
+
+    with open(in_path, "r") as fh:
+        lines = fh.readlines()
+    out = []
+    for line in lines:
+        body = line.rstrip("\n")
+        wave = _PAR_WAVE_LINE.match(body)
+        if wave:
+            ab = plain(new_values.get(wave.group(1)))
+            if isinstance(ab, dict) and "A" in ab and "B" in ab:
+                out.append("%s %s %s\n" % (wave.group(1), format(float(ab["A"]), float_fmt),
+                                           format(float(ab["B"]), float_fmt)))
+            else:
+                out.append(line)
+            continue
+        m = _PAR_LINE.match(body)
+        if not m:
+            out.append(line)
+            continue
+        key, gap, _, flag_gap, flag, old_unc, tail = m.groups()
+        v = plain(new_values.get(key))
+        if v is None or isinstance(v, dict):
+            out.append(line)
+            continue
+        text = key + gap + format(float(v), float_fmt)
+        if flag is not None:
+            text += flag_gap + flag
+            if uncertainties is not None and key in uncertainties:
+                text += " " + format(float(uncertainties[key]), uncertainty_fmt)
+            elif old_unc is not None:
+                text += " " + old_unc
+        out.append(text + tail + "\n")
+    with open(out_path, "w") as fh:
+        fh.writelines(out)
+
+
+def patch_statistics(in_path: str, out_path: str, new_stats: dict) -> None:
+    """Update the CHI2R (with its degrees of freedom, CHI2R_DOF), NTOA and TRES lines of a .par file from
+    ``new_stats``; a statistic without a line is appended at the end (readtimingmodel.py:435-484)."""
+    def render(key):
+        if key == "CHI2R":
+            dof = new_stats.get("CHI2R_DOF")
+            return "CHI2R          %s" % new_stats["CHI2R"] + ("" if dof is None else " %d" % int(dof))
+        if key == "NTOA":
+            return "NTOA           %d" % int(new_stats["NTOA"])
+        return "TRES           %s" % new_stats["TRES"]
+
+    with open(in_path, "r") as fh:
+        lines = fh.readlines()
+    out, seen = [], set()
+    for line in lines:
+        tok = line.strip().split()
+        key = tok[0].upper() if tok else None
+        if key in ("CHI2R", "NTOA", "TRES") and key in new_stats:
+            out.append(render(key) + "\n")
+            seen.add(key)
+        else:
+            out.append(line)
+    for key in ("CHI2R", "NTOA", "TRES"):
+        if key not in seen and new_stats.get(key) is not None:
+            # appended lines start on a fresh line and stay unterminated, except a CHI2R without degrees of freedom
+            bare_chi2 = key == "CHI2R" and new_stats.get("CHI2R_DOF") is None
+            out.append("\n" + render(key) + ("\n" if bare_chi2 else ""))
+    with open(out_path, "w") as fh:
+        fh.writelines(out)
+
+
+def patch_miscellaneous(in_path: str, out_path: str, new_misc: dict) -> None:
+    """Update miscellaneous keys (START, FINISH, ...) of a .par file in place, matching keys case-insensitively;
+    missing ones are appended in the order of ``new_misc``; a None value is skipped (readtimingmodel.py:487-525)."""
+    with open(in_path, "r") as fh:
+        lines = fh.readlines()
+    wanted = {k.upper(): v for k, v in new_misc.items()}
+    seen = set()
+    out = []
+    for line in lines:
+        tok = line.strip().split()
+        key = tok[0].upper() if tok else None
+        if key is not None and wanted.get(key) is not None:
+            out.append(f"{key:<15}{wanted[key]}\n")
+            seen.add(key)
+        else:
+            out.append(line)
+    for k, v in new_misc.items():
+        if v is not None and k.upper() not in seen:
+            out.append(f"\n{k.upper():<15}{v}")
+    with open(out_path, "w") as fh:
+        fh.writelines(out)

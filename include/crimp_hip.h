@@ -283,6 +283,62 @@ int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_model* model
                      const double* ph_edges, const int32_t* nph,
                      int64_t* counts, int32_t options, uint32_t flags, void* stream);
 
+/* Timing-model fits of ToAs   [utilities_fittoas.py:204-293, fit_toas.py:140-202] (csrc/timing_fit.h).
+ *
+ * model_phase_residuals (utilities_fittoas.py:269-293) evaluates a *fit model* -- every scalar that is not an epoch 0,
+ * every free parameter equal to its pvec entry, PEPOCH / fixed GLEP_* / WAVEEPOCH / WAVE_OM kept -- and takes from the
+ * *full model* the F0 that multiplies the wave sum (F0_base - dF0) and, when no wave key is free, the WAVE A/B values.
+ * The host describes that with two models per problem and one map shared by all problems of a call:
+ *   fit_base[i]:  the fit model with every free parameter 0 (its WAVE A/B: the .par values);
+ *   wave_base[i]: supplies F0_base (f[0]) and, with CRIMP_FIT_WAVES_FIXED, n_wave / WAVEEPOCH / WAVE_OM / WAVE A/B;
+ *   map->branch:  which of the reference's three branches applies;
+ *   map->slot[k]: the field parameter k overwrites; map->f0_param: the index of the F0 parameter, or -1.
+ * The models and the map are host pointers always; the arrays follow CRIMP_FLAG_DEVICE_PTRS. */
+#define CRIMP_FIT_MAX_DIM 32
+#define CRIMP_FIT_WAVES_FIXED 0 /* no wave key free: Taylor + glitches of the fit model, waves of the full model */
+#define CRIMP_FIT_WAVES_ONLY 1  /* every key is a wave key: the wave sum alone */
+#define CRIMP_FIT_WAVES_MIXED 2 /* both: Taylor + glitches + the fit model's waves */
+#define CRIMP_FIT_SLOT_F 0      /* index = n of Fn, 0..12 */
+#define CRIMP_FIT_SLOT_GLITCH 1 /* index = glitch (0-based), sub = 0..6: GLEP, GLPH, GLF0, GLF1, GLF2, GLF0D, GLTD */
+#define CRIMP_FIT_SLOT_WAVE 2   /* index = harmonic (0-based), sub = 0 (A) or 1 (B) */
+typedef struct crimp_fit_slot {
+    int32_t kind, index, sub;
+} crimp_fit_slot;
+typedef struct crimp_fit_map {
+    int32_t ndim;     /* 1..CRIMP_FIT_MAX_DIM */
+    int32_t branch;   /* CRIMP_FIT_WAVES_* */
+    int32_t f0_param; /* k with slot[k] = F0, or -1 */
+    crimp_fit_slot slot[CRIMP_FIT_MAX_DIM];
+} crimp_fit_map;
+
+/* gaussian_nll(y - mean(y), model_phase_residuals(x, parfile, pvec, keys), yerr) of nprob problems x P vectors in
+ * one launch   [utilities_fittoas.py:204-210, :236-239, :269-293]. Problem i's ToAs are [offsets[i], offsets[i+1]) of
+ * t_mjd / y / yerr (at least one each); pvec[nprob][P][ndim]; nll[nprob][P]; mu (may be NULL) = the mean-subtracted
+ * model residuals, problem i's at mu + P * offsets[i], [P][n_i]. A value depends on its ToAs and its vector alone (fixed
+ * summation order): not on P, nprob or the launch shape. CRIMP_ERR_ARG: an empty problem, ndim outside
+ * 1..CRIMP_FIT_MAX_DIM, a slot that names a field outside some problem's model. */
+int crimp_timing_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets, int64_t nprob,
+                     const crimp_timing_model* fit_base, const crimp_timing_model* wave_base,
+                     const crimp_fit_map* map, const double* pvec, int64_t P, double* nll, double* mu,
+                     uint32_t flags, void* stream);
+
+/* emcee.EnsembleSampler(W, ndim, log_probability).run_mcmc(p0, steps) of nprob problems in one launch
+ * [fit_toas.py:140-163]: the affine-invariant stretch move, a = 2, log-probability = box prior (Prior.log_prior:
+ * strict inequalities, +-inf = no bound on that side) - the NLL above, from the same device function as
+ * crimp_timing_nll (logprob equals -crimp_timing_nll(chain) bit for bit). One workgroup per problem runs all steps.
+ * The ensemble is split into fixed even / odd halves; each half is updated against the other as it stands:
+ * proposal c - (c - x) z, z = ((a-1)u + 1)^2 / a, accepted when log u' < (ndim-1) log z + lp_new - lp_old; a proposal
+ * outside the box is rejected without evaluating it, and so is one whose log-probability is not finite (the reference
+ * lets emcee raise on NaN). Random numbers: Philox4x32-10, key = seed, counter = (first_problem + i, step, walker,
+ * draw): a chain depends on the seed, the problem's global index and its own data, not on the rest of the launch.
+ * p0[nprob][W][ndim]; lo, hi [nprob][ndim]; W even, 2 ndim <= W <= 256; steps >= 1.
+ * chain[nprob][steps][W][ndim], logprob[nprob][steps][W], accepted[nprob][W] (accepted moves per walker). */
+int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                      int64_t nprob, const crimp_timing_model* fit_base, const crimp_timing_model* wave_base,
+                      const crimp_fit_map* map, const double* p0, const double* lo, const double* hi, int32_t W,
+                      int64_t steps, uint64_t seed, int64_t first_problem, double* chain, double* logprob,
+                      int64_t* accepted, uint32_t flags, void* stream);
+
 /* Interval selection of measureToAs (measureToAs.py:168-182): TIME[(TIME >= start) & (TIME <= end)] per ToA interval
  * (:173-174) and its first / last photon (ToA_mid, :182).
  * crimp_is_sorted: *unsorted = 1 if some t[i+1] < t[i] (or a NaN), else 0 (host int; t host or device per flags).
