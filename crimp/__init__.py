@@ -1,9 +1,10 @@
 """``crimp`` import name for the MI355X build: ``from crimp.periodsearch import PeriodSearch`` and every other
 ``crimp.<module>`` this build provides resolve to the drop-in module ``crimp_amd.<module>`` (the same module object,
 so state and classes are shared): the photon hot path (``calcphase``, ``periodsearch``, ``templatemodels``,
-``measureToAs``, ``pulseprofile``, ``eventfile``, ``timfile``, ...) and the timing-model fits of the ToAs
-(``fit_toas``, ``utilities_fittoas``, ``get_local_ephem``, ``plot_local_ephem``). Modules the build does not provide
-(``diagnoseToAs``, ``merge_overlapping_timfiles``, the simulator) raise ImportError as a missing module would. The
+``measureToAs``, ``pulseprofile``, ``eventfile``, ``timfile``, ...), the timing-model fits of the ToAs
+(``fit_toas``, ``utilities_fittoas``, ``get_local_ephem``, ``plot_local_ephem``) and the event simulator
+(``simulatemodulatedlc``). Modules the build does not provide (``diagnoseToAs``, ``merge_overlapping_timfiles``) raise
+ImportError as a missing module would. The
 pulse-profile plots are provided as ``crimp_amd.plot_pps`` (and the ``pulseprofile_plots`` script) only, as
 tests/test_capi_and_host.py::test_crimp_import_name_and_entry_points pins it (``crimp.plot_pps`` raises)."""
 import importlib

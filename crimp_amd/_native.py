@@ -78,12 +78,21 @@ class Template(ctypes.Structure):
                 ("i0", ctypes.c_double * MAX_COMP), ("amp_shift", ctypes.c_double)]
 
 
+SIM_TEMPLATE, SIM_STEPS = 0, 1
+
+
+class SimShape(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("tpl", Template), ("norm", ctypes.c_double),
+                ("ph_shift", ctypes.c_double), ("steps", ctypes.c_void_p), ("bkg", ctypes.c_double),
+                ("lam_max", ctypes.c_double)]
+
+
 EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_last_kernel_times", "crimp_last_fixups",
            "crimp_last_search_path", "crimp_last_nufft_plan", "crimp_last_nufft_work", "crimp_last_toa_grid_norms", "crimp_last_toa_grid_fast", "crimp_release_scratch",
            "crimp_device_count", "crimp_calcphase", "crimp_search", "crimp_search_best", "crimp_best", "crimp_search_sets", "crimp_toa_points",
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
-           "crimp_gather_ranges")
+           "crimp_gather_ranges", "crimp_sim_events")
 
 _lib = None
 _lock = threading.Lock()
@@ -131,6 +140,9 @@ def load(require_device=True):
             L.crimp_is_sorted.argtypes = [P, i64, ctypes.POINTER(i32), u32, P]
             L.crimp_select_intervals.argtypes = [P, i64, P, P, i64, P, P, P, u32, P]
             L.crimp_gather_ranges.argtypes = [P, i64, P, P, i64, P, u32, P]
+            L.crimp_sim_events.argtypes = [MP, ctypes.POINTER(SimShape), ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, P, i64, ctypes.c_uint64, i64, i64, P, P, i64,
+                                           ctypes.POINTER(i64), ctypes.c_double, u32, P]
             L.crimp_toa_redchi2.argtypes = [P, P, i64, ctypes.POINTER(Template), P, P, P, P, i32, i32, P, u32, P]
             L.crimp_toa_fit_redchi2.argtypes = [P, P, i64, ctypes.POINTER(Template), P, ctypes.c_double, i32, i32, P, P,
                                                 i32, i32, P, P, u32, P]

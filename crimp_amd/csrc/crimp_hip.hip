@@ -1486,6 +1486,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "toa_shape.h"
 #include "phase_cube.h"
 #include "timing_fit.h"
+#include "sim_events.h"
 
 // ============================================================== 6. C-ABI
 static hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -3750,6 +3751,121 @@ extern "C" int crimp_gather_ranges(const double* t, int64_t n, const int64_t* lo
         k_gather_ranges<<<(unsigned)nint, 256, 0, s>>>(dt, dlo, doff, dout);
         HIPCHK(hipGetLastError());
         HIPCHK(copy_back(s, out, dout, (size_t)total, dev));
+    }
+    return finish(s, flags);
+}
+
+// ============================================================== 8. event simulator (sim_events.h)
+extern "C" int crimp_sim_events(const crimp_timing_model* model, const crimp_sim_shape* shape, double mjd_start,
+                                double span_s, double cell_s, const double* gti, int64_t ngti, uint64_t seed,
+                                int64_t first_cell, int64_t n_cells, double* t_out, uint8_t* bkg_out, int64_t cap,
+                                int64_t* n_out, double out_offset_s, uint32_t flags, void* stream) {
+    ARGCHK(model != nullptr && shape != nullptr && n_out != nullptr, "null argument");
+    *n_out = 0;
+    ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
+    ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+    ARGCHK(std::isfinite(mjd_start) && std::isfinite(out_offset_s), "mjd_start and out_offset_s must be finite");
+    ARGCHK(std::isfinite(span_s) && span_s > 0.0, "span_s must be positive and finite");
+    ARGCHK(std::isfinite(cell_s) && cell_s > 0.0, "cell_s must be positive and finite");
+    ARGCHK(std::isfinite(shape->lam_max) && shape->lam_max > 0.0, "lam_max must be positive and finite");
+    ARGCHK(shape->lam_max * cell_s <= 65536.0, "lam_max * cell_s > 65536: shorten the cells");
+    ARGCHK(std::isfinite(shape->bkg) && shape->bkg >= 0.0, "the background rate must be finite and >= 0");
+    ARGCHK(shape->kind == CRIMP_SIM_TEMPLATE || shape->kind == CRIMP_SIM_STEPS, "unknown shape kind");
+    ARGCHK(ngti >= 0 && (ngti == 0 || gti != nullptr), "ngti < 0 or a null GTI table");
+    ARGCHK(cap >= 0 || t_out == nullptr, "cap < 0");
+    SimArgs A{};
+    A.kind = shape->kind;
+    if (shape->kind == CRIMP_SIM_TEMPLATE) {
+        const int rc = make_tpl(&shape->tpl, &A.T);
+        if (rc != CRIMP_OK) return rc;
+        ARGCHK(std::isfinite(shape->norm) && std::isfinite(shape->ph_shift), "norm and ph_shift must be finite");
+    } else {
+        ARGCHK(shape->n_steps >= 1 && shape->steps != nullptr, "a step shape needs n_steps >= 1 rates");
+        A.n_steps = shape->n_steps;
+    }
+    // cells: the smallest count whose cells cover [0, span_s), every cell starting inside the span
+    const double ncd = std::ceil(span_s / cell_s);
+    ARGCHK(ncd < 2147483648.0, "more than 2^31 - 1 cells: lengthen the cells");
+    int64_t nc = std::max<int64_t>((int64_t)ncd, 1);
+    while (nc > 1 && (double)(nc - 1) * cell_s >= span_s) --nc;
+    while ((double)nc * cell_s < span_s) ++nc;
+    ARGCHK(nc <= 2147483647LL, "more than 2^31 - 1 cells: lengthen the cells");
+    ARGCHK(first_cell >= 0 && first_cell <= nc, "first_cell outside the span's cells");
+    if (n_cells < 0) n_cells = nc - first_cell;
+    ARGCHK(first_cell + n_cells <= nc, "the cell range ends outside the span's cells");
+    A.norm = shape->norm;
+    A.ph_shift = shape->ph_shift;
+    A.bkg = shape->bkg;
+    A.lam_max = shape->lam_max;
+    A.inv_lam = 1.0 / shape->lam_max;
+    A.mjd_start = mjd_start;
+    A.span_s = span_s;
+    A.cell_s = cell_s;
+    A.out_offset_s = out_offset_s;
+    A.first_cell = first_cell;
+    A.ngti = ngti;
+    A.seed = seed;
+    A.days = (flags & CRIMP_FLAG_TIME_DAYS) ? 1 : 0;
+    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
+    std::lock_guard<std::mutex> lk(g_mutex);
+    if (flags & CRIMP_FLAG_TIME_KERNELS) {
+        g_kernel_times.clear();
+        g_last_kernel_ms = -1.0;
+    }
+    hipStream_t s = as_stream(stream);
+    if (ngti > 0) {  // the table is checked on the host before anything is queued
+        std::vector<double> hg((size_t)ngti * 2);
+        if (dev)
+            HIPCHK(d2h(s, hg.data(), gti, hg.size() * sizeof(double)));
+        else
+            std::memcpy(hg.data(), gti, hg.size() * sizeof(double));
+        for (int64_t i = 0; i < ngti; ++i) {
+            ARGCHK(hg[2 * i] <= hg[2 * i + 1], "a GTI ends before it starts (or holds a NaN)");
+            ARGCHK(i == 0 || hg[2 * i - 1] <= hg[2 * i], "the GTIs must be sorted and disjoint");
+        }
+    }
+    if (n_cells == 0) return CRIMP_OK;  // an empty cell range: no events, every argument checked all the same
+    CPModel hm{};
+    make_cpmodel(model, 7, &hm);
+    {
+        Scratch sc(s);
+        const double *dgti = nullptr, *dsteps = nullptr;
+        HIPCHK(stage_in(sc, gti, (size_t)ngti * 2, dev, &dgti));
+        if (A.kind == CRIMP_SIM_STEPS) HIPCHK(stage_in(sc, shape->steps, (size_t)A.n_steps, dev, &dsteps));
+        const int64_t n1 = n_cells + 1;  // the counts and one trailing zero: the scan leaves the total there
+        const int64_t tiles = cdiv(n1, kSimScanTile);
+        int64_t *dcnt = nullptr, *dsums = nullptr;
+        HIPCHK(sc.alloc(&dcnt, (size_t)n1));
+        HIPCHK(sc.alloc(&dsums, (size_t)tiles));
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        HIPCHK(hipMemsetAsync(dcnt + n_cells, 0, sizeof(int64_t), s));
+        k_sim_cells<false><<<(unsigned)n_cells, 64, 0, s>>>(hm, A, dsteps, dgti, dcnt, nullptr, nullptr, nullptr);
+        HIPCHK(hipGetLastError());
+        k_sim_tile_sums<<<(unsigned)tiles, kSimScanBlock, 0, s>>>(dcnt, n1, dsums);
+        k_sim_scan_top<<<1, kSimScanBlock, 0, s>>>(dsums, tiles);
+        k_sim_scan_apply<<<(unsigned)tiles, kSimScanBlock, 0, s>>>(dcnt, n1, dsums);
+        HIPCHK(hipGetLastError());
+        int64_t total = 0;
+        HIPCHK(d2h(s, &total, dcnt + n_cells, sizeof(int64_t)));
+        *n_out = total;
+        if (t_out == nullptr) {
+            kt.stop();
+            return finish(s, flags);
+        }
+        if (cap < total) kt.stop();  // the count pass and the scan ran: their time is reported as on the count-only path
+        ARGCHK(cap >= total, "cap is smaller than the number of events (nothing written)");
+        double* dt = nullptr;
+        uint8_t* db = nullptr;
+        HIPCHK(stage_out(sc, t_out, (size_t)total, dev, &dt));
+        HIPCHK(stage_out(sc, bkg_out, (size_t)total, dev, &db));
+        if (total > 0) {
+            k_sim_cells<true><<<(unsigned)n_cells, 64, 0, s>>>(hm, A, dsteps, dgti, nullptr, dcnt, dt, db);
+            HIPCHK(hipGetLastError());
+        }
+        kt.stop();
+        HIPCHK(copy_back(s, t_out, dt, (size_t)total, dev));
+        HIPCHK(copy_back(s, bkg_out, db, (size_t)total, dev));
     }
     return finish(s, flags);
 }

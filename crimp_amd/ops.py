@@ -580,3 +580,108 @@ def gather_ranges(t, lo, offsets):
     with b.device_guard():
         N.check(L.crimp_gather_ranges(tp, n, lp, op, nint, outp, b.flags(), b.stream()))
     return out
+
+
+def make_sim_shape(template=None, norm=0.0, ph_shift=0.0, steps=None, bkg=0.0, lam_max=None):
+    """crimp_sim_shape of the event simulator: a template shape (``template`` a crimp_template from make_template,
+    with ``norm`` in counts/s and ``ph_shift`` in rad) or a step shape (``steps``: one rate per phase bin), a flat
+    background ``bkg`` and the caller's rate bound ``lam_max`` >= shape + bkg at every phase."""
+    if (template is None) == (steps is None):
+        raise ValueError("a simulated shape is either a template or a table of steps")
+    if lam_max is None:
+        raise ValueError("lam_max (a bound of the rate) is required")
+    sh = N.SimShape()
+    if template is not None:
+        sh.kind = N.SIM_TEMPLATE
+        sh.tpl = template
+        sh.norm, sh.ph_shift = float(norm), float(ph_shift)
+        sh._steps = None
+    else:
+        arr = np.ascontiguousarray(steps, dtype=np.float64).reshape(-1)
+        sh.kind = N.SIM_STEPS
+        sh.n_steps = int(arr.size)
+        sh.steps = arr.ctypes.data if arr.size else None
+        sh._steps = arr  # keeps the table alive
+    sh.bkg, sh.lam_max = float(bkg), float(lam_max)
+    return sh
+
+
+def sim_events(model, shape, mjd_start, span_s, cell_s, gti=None, seed=0, first_cell=0, n_cells=-1, out_offset_s=0.0,
+               days=False, want_bkg=True, device=None, count_only=False, flags=0, cap=None):
+    """Simulated events of crimp_sim_events: (time, is_bgr, n). ``model``: a timing-model dict (or N.TimingModel);
+    ``shape``: make_sim_shape's; ``gti`` [ngti, 2] MJD or None. The count pass sizes the buffers, the fill pass writes
+    them: NumPy arrays, or tensors on ``device`` (True: the current GPU) -- then nothing but the count crosses to the
+    host. ``time`` is ``out_offset_s`` + seconds since ``mjd_start``, or MJD with ``days``; ``is_bgr`` uint8 (None
+    without ``want_bkg``); ``count_only``: (None, None, n). ``cap``: the caller's estimate of the number of events --
+    buffers of that size are tried first, so that a sufficient estimate saves the separate count call (the outputs are
+    then views of the larger buffers)."""
+    L = N.load()
+    m = model if isinstance(model, N.TimingModel) else _modeltm(model)
+    g = None if gti is None else np.ascontiguousarray(gti, dtype=np.float64).reshape(-1, 2)
+    ngti = 0 if g is None else int(g.shape[0])
+    fl = int(flags) | (N.FLAG_TIME_DAYS if days else 0)
+    sh = N.SimShape.from_buffer_copy(shape)
+    steps = getattr(shape, "_steps", None)
+    keep = [steps, g]
+    stream = None
+    guard = None
+    if device is not None and device is not False:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is True else torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        fl |= N.FLAG_DEVICE_PTRS
+        guard = torch.cuda.device(dev)
+        if steps is not None and steps.size:
+            sd = torch.as_tensor(steps, device=dev)
+            keep.append(sd)
+            sh.steps = sd.data_ptr()
+        gd = torch.as_tensor(g, device=dev) if ngti else None
+        keep.append(gd)
+        gp = ctypes.c_void_p(gd.data_ptr()) if ngti else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    else:
+        dev = None
+        gp = ctypes.c_void_p(g.ctypes.data) if ngti else None
+    n = ctypes.c_int64(0)
+
+    def empty(k):
+        if dev is not None:
+            import torch
+            return (torch.empty(k, dtype=torch.float64, device=dev),
+                    torch.empty(k, dtype=torch.uint8, device=dev) if want_bkg else None)
+        return np.empty(k, dtype=np.float64), (np.empty(k, dtype=np.uint8) if want_bkg else None)
+
+    def ptr(a):
+        if a is None:
+            return None
+        return ctypes.c_void_p(a.data_ptr() if dev is not None else a.ctypes.data)
+
+    def call(t, b, size, may_overflow=False):
+        args = (ctypes.byref(m), ctypes.byref(sh), float(mjd_start), float(span_s), float(cell_s), gp, ngti,
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_cell), int(n_cells), ptr(t), ptr(b), int(size),
+                ctypes.byref(n), float(out_offset_s), fl, stream)
+        if guard is not None:
+            with guard:
+                rc = L.crimp_sim_events(*args)
+        else:
+            rc = L.crimp_sim_events(*args)
+        if may_overflow and rc == -1 and n.value > size:  # CRIMP_ERR_ARG: the estimate was too small
+            return False
+        N.check(rc)
+        return True
+
+    if g is not None and ngti == 0:  # no good time at all
+        t, b = empty(0)
+        return (None, None, 0) if count_only else (t, b, 0)
+    if cap is not None and not count_only and int(cap) > 0:
+        t, b = empty(int(cap))
+        if call(t, b, int(cap), may_overflow=True):
+            k = int(n.value)
+            return t[:k], (None if b is None else b[:k]), k
+    call(None, None, 0)
+    if count_only:
+        return None, None, int(n.value)
+    t, b = empty(int(n.value))
+    call(t, b, int(n.value))
+    return t, b, int(n.value)

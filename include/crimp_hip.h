@@ -353,6 +353,47 @@ int crimp_select_intervals(const double* t, int64_t n, const double* starts, con
 int crimp_gather_ranges(const double* t, int64_t n, const int64_t* lo, const int64_t* offsets, int64_t nint,
                         double* out, uint32_t flags, void* stream);
 
+/* Event simulator   [simulatemodulatedlc.py:19-96: the binned sinusoid at constant frequency drawn from NumPy's global
+ * RNG, :64-79 its per-bin Poisson counts and uniform phases, :88-92 its flat background; and this build's host
+ * generators crimp_amd/synth.py pulsed_events / template_phases] (csrc/sim_events.h).
+ *
+ * Events on [mjd_start, mjd_start + span_s / 86400), restricted to the union of the half-open GTIs [start, stop) when
+ * given, form an inhomogeneous Poisson process of rate lambda(t) = S(frac(phi(t))) + bkg counts/s: phi(t) is what
+ * crimp_calcphase computes for that MJD (parts = 7), S the source shape --
+ *   CRIMP_SIM_TEMPLATE: norm + the template part of `tpl` at ph_shift (amp_shift in tpl), the model value of
+ *     templatemodels.py:64-82, :166-185, :271-290 as crimp_toa_points forms it (x in cycles for Fourier, radians
+ *     otherwise; the fit's sign of phShift: crimp_toa_fit on simulated events returns ph_shift);
+ *   CRIMP_SIM_STEPS: steps[k] on the phase bin [k / n_steps, (k + 1) / n_steps)  (simulatemodulatedlc.py:64-79).
+ * lam_max is the caller's bound: S + bkg <= lam_max at every phase (the library thins candidates of rate lam_max and
+ * trusts it). Time is cut into cells of cell_s seconds anchored at mjd_start; the events of a cell depend on (seed,
+ * model, shape, mjd_start, span_s, cell_s, GTIs, the cell's index) alone, so the calls over [first_cell, first_cell +
+ * n_cells) of any partition concatenate to the whole list bit for bit (n_cells = -1: every cell from first_cell on).
+ *   t_out == NULL: the count pass alone, *n_out = the number of events. Otherwise cap < that number fails with
+ *   CRIMP_ERR_ARG (nothing written, *n_out still set); else t_out[n] non-decreasing = out_offset_s + seconds since
+ *   mjd_start, or the MJD mjd_start + s / 86400 with CRIMP_FLAG_TIME_DAYS; bkg_out[n] (may be NULL) = 1 for a
+ *   background event (u lam_max >= S), 0 for a source event.
+ * model, shape and n_out are host pointers always; shape->steps, gti, t_out and bkg_out follow CRIMP_FLAG_DEVICE_PTRS.
+ * gti[ngti][2] MJD, sorted and disjoint (NULL / 0: the whole span). CRIMP_FLAG_TIME_KERNELS times the count pass, the
+ * scan and the fill pass together (crimp_last_kernel_ms). CRIMP_ERR_ARG: span_s <= 0, a non-finite or non-positive
+ * lam_max or cell_s, lam_max * cell_s > 65536, unsorted or overlapping GTIs, n_steps < 1, a cell range outside the
+ * span's cells, more than 2^31 - 1 cells. */
+#define CRIMP_SIM_TEMPLATE 0
+#define CRIMP_SIM_STEPS 1
+typedef struct crimp_sim_shape {
+    int32_t kind;         /* CRIMP_SIM_TEMPLATE | CRIMP_SIM_STEPS */
+    int32_t n_steps;      /* steps: number of rates */
+    crimp_template tpl;   /* template */
+    double norm;          /* template: norm (counts/s) */
+    double ph_shift;      /* template: phShift (rad) */
+    const double* steps;  /* steps: n_steps rates (counts/s) */
+    double bkg;           /* flat background b >= 0 (counts/s) */
+    double lam_max;       /* bound of S + bkg */
+} crimp_sim_shape;
+int crimp_sim_events(const crimp_timing_model* model, const crimp_sim_shape* shape, double mjd_start, double span_s,
+                     double cell_s, const double* gti, int64_t ngti, uint64_t seed, int64_t first_cell,
+                     int64_t n_cells, double* t_out, uint8_t* bkg_out, int64_t cap, int64_t* n_out,
+                     double out_offset_s, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
