@@ -298,7 +298,7 @@ __device__ __forceinline__ void sincos_rev_poly(float r, float& s, float& c) {
 struct CPModel {
     double pepoch;
     double coef[13];  // (1/n!) * F_{n-1}, exactly as calcphase.py:84 forms it
-    int32_t nterms;   // highest n with a non-zero coefficient
+    int32_t nterms;   // highest n with a non-zero coefficient, at least 1 (make_cpmodel)
     int32_t parts;
     int32_t n_glitch;
     int32_t n_wave;
@@ -1548,6 +1548,9 @@ static void make_cpmodel(const crimp_timing_model* model, int32_t parts, CPModel
         hm.coef[k] = (1.0 / fact) * model->f[k];
         if (model->f[k] != 0.0) hm.nterms = k + 1;
     }
+    // with every F zero the first term stays: 0 * dt adds nothing to a finite time and carries a NaN time into the
+    // total as the reference's 0 * NaN does (no comparison t >= GLEP is true for a NaN, so the glitch sum alone is 0)
+    if (hm.nterms == 0) hm.nterms = 1;
     hm.parts = parts;
     hm.n_glitch = model->n_glitch;
     std::memcpy(hm.glitch, model->glitch, sizeof(hm.glitch));
@@ -1561,7 +1564,8 @@ static void make_cpmodel(const crimp_timing_model* model, int32_t parts, CPModel
 extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timing_model* model, int32_t parts,
                                double* total, double* folded, uint32_t flags, void* stream) {
     ARGCHK(n >= 0, "n < 0");
-    ARGCHK(model != nullptr && total != nullptr && (t_mjd != nullptr || n == 0), "null argument");
+    // n == 0 takes null arrays: an empty torch tensor's data pointer is null
+    ARGCHK(model != nullptr && ((total != nullptr && t_mjd != nullptr) || n == 0), "null argument");
     ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
     ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
     if (n == 0) return CRIMP_OK;

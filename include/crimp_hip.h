@@ -143,7 +143,9 @@ int crimp_device_count(int32_t* count);
 
 /* calcphase(timeMJD, timMod) -> (total, folded)   [calcphase.py:152-176]
  * parts: bit0 Taylor expansion (:73-85), bit1 glitches (:87-126), bit2 waves (:128-149);
- * 7 = calcphase(). folded may be NULL. */
+ * 7 = calcphase(). folded may be NULL. n == 0 succeeds without touching anything, and t_mjd and total may then be
+ * NULL as well (the data pointer of an empty array). A NaN time gives NaN in total and folded whenever bit0 is set,
+ * with every F term zero too (the reference's 0 * NaN). */
 int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timing_model* model, int32_t parts,
                     double* total, double* folded, uint32_t flags, void* stream);
 
