@@ -21,7 +21,6 @@
 #include <mutex>
 #include <string>
 #include <chrono>
-#include <functional>
 #include <vector>
 
 #include "../../include/crimp_hip.h"
@@ -263,6 +262,90 @@ static hipError_t d2h(hipStream_t s, void* h, const void* d, size_t bytes) {
     return hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost);
 }
 
+static hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The prologue of every computing entry point: calls are serialised by g_mutex for their whole length, the pointer
+// and timing flags decoded, the kernel-time record of the previous call cleared when this one is timed. kKeepTimes:
+// the entries that record no kernel times (crimp_best and the interval selection) leave the last record standing.
+struct Call {
+    enum Times { kResetTimes, kKeepTimes };
+    std::lock_guard<std::mutex> lk;
+    const bool dev, timed;  // CRIMP_FLAG_DEVICE_PTRS, CRIMP_FLAG_TIME_KERNELS
+    const hipStream_t s;
+    Call(uint32_t flags, void* stream, Times times = kResetTimes)
+        : lk(g_mutex), dev(flags & CRIMP_FLAG_DEVICE_PTRS), timed(flags & CRIMP_FLAG_TIME_KERNELS),
+          s(as_stream(stream)) {
+        if (timed && times == kResetTimes) {
+            g_kernel_times.clear();
+            g_last_kernel_ms = -1.0;
+        }
+    }
+};
+
+// offsets[n + 1] on the host: offsets[0] >= 0 and non-decreasing, or increasing where strict (every span holds
+// something); otherwise CRIMP_ERR_ARG with the entry's own text. *max_span: the largest span.
+static int check_offsets(const std::vector<int64_t>& h, bool strict, const char* msg, int64_t* max_span = nullptr) {
+    int64_t m = 0;
+    ARGCHK(h[0] >= 0, msg);
+    for (size_t i = 0; i + 1 < h.size(); ++i) {
+        ARGCHK(strict ? h[i + 1] > h[i] : h[i + 1] >= h[i], msg);
+        m = std::max(m, h[i + 1] - h[i]);
+    }
+    if (max_span) *max_span = m;
+    return CRIMP_OK;
+}
+// the table copied from the caller's device or host pointer (the stream drained once), then checked
+static int read_offsets(const Call& c, const int64_t* offsets, int64_t n, bool strict, const char* msg,
+                        std::vector<int64_t>* h, int64_t* max_span = nullptr) {
+    h->resize((size_t)n + 1);
+    if (c.dev)
+        HIPCHK(d2h(c.s, h->data(), offsets, h->size() * sizeof(int64_t)));
+    else
+        std::memcpy(h->data(), offsets, h->size() * sizeof(int64_t));
+    return check_offsets(*h, strict, msg, max_span);
+}
+
+// Several small tables of the caller's to the host with one stream drain: async reads into the page-locked staging
+// buffer (pin_begin) where they fit, blocking copies otherwise; plain copies from host pointers. Empty reads are
+// skipped.
+struct HostRead {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+static hipError_t read_list(const Call& c, std::initializer_list<HostRead> reads) {
+    const auto slot = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    size_t need = 0;
+    for (const HostRead& r : reads) need += slot(r.bytes);
+    const bool pinned = c.dev && g_pin.p && need <= g_pin.cap;
+    if (c.dev && !pinned) {
+        const hipError_t e = hipStreamSynchronize(c.s);
+        if (e != hipSuccess) return e;
+    }
+    char* q = g_pin.p;
+    for (const HostRead& r : reads) {
+        if (r.bytes == 0) continue;
+        hipError_t e = hipSuccess;
+        if (pinned)
+            e = hipMemcpyAsync(q, r.src, r.bytes, hipMemcpyDeviceToHost, c.s);
+        else if (c.dev)
+            e = hipMemcpy(r.dst, r.src, r.bytes, hipMemcpyDeviceToHost);
+        else
+            std::memcpy(r.dst, r.src, r.bytes);
+        if (e != hipSuccess) return e;
+        if (pinned) q += slot(r.bytes);
+    }
+    if (!pinned) return hipSuccess;
+    const hipError_t e = hipStreamSynchronize(c.s);
+    if (e != hipSuccess) return e;
+    q = g_pin.p;
+    for (const HostRead& r : reads) {
+        if (r.bytes) std::memcpy(r.dst, q, r.bytes);
+        q += slot(r.bytes);
+    }
+    return hipSuccess;
+}
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ============================================================== 2. sin/cos in revolutions
@@ -496,14 +579,7 @@ __global__ __launch_bounds__(256) void k_search_finalize(const double* __restric
 #include "search_exact.h"
 
 // ============================================================== 5. ToA likelihood scan
-struct TplDev {
-    int32_t model, K;
-    double amp[CRIMP_MAX_COMP];   // amp_j * ampShift (fourier), amp_j*ampShift/(2 pi) * sinh(w) (cauchy),
-                                  // amp_j*ampShift/(2 pi I0(1/w^2)) (vonmises)
-    double loc[CRIMP_MAX_COMP];   // ph_j or cen_j
-    double ch[CRIMP_MAX_COMP];    // cosh(wid_j) (cauchy)
-    double kap[CRIMP_MAX_COMP];   // 1/wid_j^2 (vonmises)
-};
+#include "toa_grid_plan.h"  // TplDev, the brute grid's host plan (plan_brute_grid) and its constants
 
 constexpr int kPtsPerGroup = 4;
 #ifndef CRIMP_PTS_BLOCK
@@ -778,11 +854,9 @@ __global__ __launch_bounds__(kPtsBlock) void k_toa_points(const double* __restri
 // so the sums are bit-identical to the scalar form.
 constexpr int kGridBlock = 128;
 constexpr int kGridNN = 20;
-constexpr int kGridKMax = 8;
 constexpr int kGridProd = 4;
 constexpr int64_t kGridTarget = 16384;  // brute-grid blocks per launch (toa_grid_partials)
 static_assert(kGridNN % 2 == 0 && kGridProd == 4, "norm pairs; photons in two pairs per product");
-constexpr int kGridNNSmall = 4;  // the pruned brute grid's norms per lane (crimp_toa_fit)
 #ifndef CRIMP_GRID_MFMA
 #define CRIMP_GRID_MFMA 1  // Fourier brute grid on the f16 matrix cores (k_toa_grid_mf)
 #endif
@@ -1348,6 +1422,45 @@ static int64_t bin_splits(int64_t ntot, int64_t nint) {
     return std::max<int64_t>(1, std::min<int64_t>({(2048 + nint - 1) / nint, (per + 4095) / 4096, 65535}));
 }
 
+// redChi2 of every fitted interval on the device (measureToAs.py:385-393 and the Cauchy / von Mises copies): against
+// binphases' histogram (k_binphases, np.histogram semantics) the best-fit template curve at the bin centres;
+// chi2 = sum_b (model_b - rate_b)^2 / err_b^2 with rate = cts / (E / nbins), err = sqrt(cts) / (E / nbins) (numpy's
+// division: an empty bin gives inf, or nan where the model is 0 too), summed in bin order, redChi2 = chi2 / (nbins -
+// nfree). One 64-thread block per interval; rec = the fit records (norm [0], phShift [1], ampShift [6]).
+__global__ __launch_bounds__(64) void k_toa_chi2(const unsigned long long* __restrict__ counts, const TplDev T,
+                                                 const double* __restrict__ expo, const double* __restrict__ rec,
+                                                 const double* __restrict__ centers, int nb, int nfree,
+                                                 double* __restrict__ out) {
+    __shared__ double term[256];
+    const int64_t iv = blockIdx.x;
+    const double n = rec[iv * 8], ph = rec[iv * 8 + 1], A = rec[iv * 8 + 6];
+    const double w = expo[iv] / (double)nb;
+    for (int b = threadIdx.x; b < nb; b += 64) {
+        const double xx = centers[b];
+        double y = n;  // toafit.ToAFitter.curve: fourseries / wrapcauchy / vonmises (templatemodels.py:64-82, :166-185,
+                       // :271-290); Fourier by angle subtraction as the host formed it
+        for (int j = 0; j < T.K; ++j) {
+            if (T.model == CRIMP_MODEL_FOURIER) {
+                const double ang = (double)(j + 1) * 2.0 * M_PI * xx + T.loc[j], bph = (double)(j + 1) * ph;
+                y = y + T.amp[j] * A * (cos(ang) * cos(bph) + sin(ang) * sin(bph));
+            } else if (T.model == CRIMP_MODEL_CAUCHY) {
+                y = y + T.amp[j] * A / (T.ch[j] - cos(xx - T.loc[j] - ph));
+            } else {
+                y = y + T.amp[j] * A * exp(T.kap[j] * cos(xx - T.loc[j] - ph));
+            }
+        }
+        const double c = (double)counts[iv * nb + b];
+        const double rate = c / w, err = sqrt(c) / w;
+        term[b] = ((y - rate) * (y - rate)) / (err * err);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double chi2 = 0.0;
+        for (int b = 0; b < nb; ++b) chi2 += term[b];
+        out[iv] = chi2 / (double)(nb - nfree);
+    }
+}
+
 // Many independent one-trial searches (measureToAs.py:210-212: PeriodSearch(TIME_toa*86400, [f(ToA_mid)], 5).htest()
 // per interval): set i is t[offsets[i] : offsets[i+1]] with its own t0 = (t[first] + t[last])/2 (periodsearch.py:54)
 // and trial frequency freq[i]. One block per set; fp64 as k_search_f64 (harmonic groups of 8 from exact phases,
@@ -1489,7 +1602,6 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "sim_events.h"
 
 // ============================================================== 6. C-ABI
-static hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 // A second stream per device for crimp_toa_fit's overlapped halves (created once, kept for the process)
 static hipStream_t aux_stream() {
     static hipStream_t st[64] = {};
@@ -1569,13 +1681,9 @@ extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timin
     ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
     ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
     if (n == 0) return CRIMP_OK;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     CPModel hm{};
     make_cpmodel(model, parts, &hm);
     {
@@ -1978,9 +2086,9 @@ extern "C" int crimp_best(const double* x, int64_t n, double* best, uint32_t fla
     ARGCHK(n >= 1, "need at least one value");
     ARGCHK(x != nullptr && best != nullptr, "null argument");
     ARGCHK(n <= (int64_t(1) << 53), "n above 2^53 (the index is returned as a double)");
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream, Call::kKeepTimes);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     {
         Scratch sc(s);
         const double* dx = nullptr;
@@ -2047,13 +2155,9 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
     // the NUFFT is tried first unless a precision flag excludes it (CRIMP_FLAG_NUFFT asks for the default explicitly)
     const bool nufft = !f64 && !exact_only;
     if (count == 0) return CRIMP_OK;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     g_last_fixups = 0;
     {
         Scratch sc(s);
@@ -2185,21 +2289,13 @@ extern "C" int crimp_search_sets(const double* t, const int64_t* offsets, int64_
     ARGCHK(t != nullptr && offsets != nullptr && freq != nullptr && out != nullptr, "null argument");
     ARGCHK(nset <= 2147483647LL, "too many sets");
     if (nset == 0) return CRIMP_OK;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
-    std::vector<int64_t> hoff((size_t)nset + 1);
-    if (dev) {
-        HIPCHK(d2h(s, hoff.data(), offsets, (nset + 1) * sizeof(int64_t)));
-    } else {
-        std::memcpy(hoff.data(), offsets, (nset + 1) * sizeof(int64_t));
-    }
-    for (int64_t i = 0; i < nset; ++i)
-        ARGCHK(hoff[i + 1] > hoff[i] && hoff[i] >= 0, "every set needs photons (periodsearch.py:54 reads time[0])");
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    std::vector<int64_t> hoff;
+    const int rc = read_offsets(call, offsets, nset, true, "every set needs photons (periodsearch.py:54 reads time[0])",
+                                &hoff);
+    if (rc) return rc;
     {
         Scratch sc(s);
         const double *dt = nullptr, *df = nullptr;
@@ -2245,104 +2341,6 @@ static int make_tpl(const crimp_template* tpl, TplDev* T) {
     return CRIMP_OK;
 }
 
-// Bounds hmin <= h <= hmax of the template part h = model - norm over every phase and phShift
-// (templatemodels.py:64-82, :166-185, :271-290 with TplDev's folded amplitudes)
-// A lower bound of the template part h over every phase and phShift, from the template's own shape: min over u of
-// h(u) (h(x; phShift) is h shifted in phase for every model, so its minimum does not depend on phShift) sampled on
-// 2^16 points per turn, less the largest change between neighbouring samples (a smooth h cannot dip further between
-// two samples than it moves across one step). Tighter than tpl_bounds' -sum|amp_j| for Fourier templates.
-static double tpl_hmin_scan_uncached(const TplDev& T);
-static double tpl_hmin_scan(const TplDev& T) {  // cached for the last template (a fit batch reuses one template)
-    static TplDev last;
-    static double val = 0.0;
-    static bool have = false;
-    if (have && std::memcmp(&last, &T, sizeof(T)) == 0) return val;
-    val = tpl_hmin_scan_uncached(T);
-    std::memcpy(&last, &T, sizeof(T));
-    have = true;
-    return val;
-}
-static double tpl_hmin_scan_uncached(const TplDev& T) {
-    const int M = 1 << 16;
-    double mn = INFINITY, dmax = 0.0, prev = 0.0, first = 0.0;
-    for (int i = 0; i <= M; ++i) {
-        const double u = 2.0 * M_PI * (double)(i % M) / (double)M;
-        double h = 0.0;
-        for (int j = 0; j < T.K; ++j) {
-            if (T.model == CRIMP_MODEL_FOURIER)
-                h += T.amp[j] * std::cos((double)(j + 1) * u + T.loc[j]);
-            else if (T.model == CRIMP_MODEL_CAUCHY)
-                h += T.amp[j] / (T.ch[j] - std::cos(u - T.loc[j]));
-            else
-                h += T.amp[j] * std::exp(T.kap[j] * std::cos(u - T.loc[j]));
-        }
-        if (i == 0) first = h;
-        if (i > 0) dmax = std::max(dmax, std::fabs(h - prev));
-        mn = std::min(mn, h);
-        prev = h;
-    }
-    (void)first;
-    return mn - dmax - 1e-12 * (std::fabs(mn) + dmax);
-}
-
-// Lazy-norm certificate (crimp_toa_fit_redchi2): per phShift phi_k of the brute lattice and histogram bin b = [e_b,
-// e_{b+1}], an upper bound of the Fourier template part over every photon bin b can hold at phi_k,
-// max_{x in bin} h0(x - phi_k / 2 pi) with h0(u) = sum_j amp_j cos(2 pi (j+1) u + loc_j) (k_toa_grid_mf's h): the
-// largest of 8192 samples per cycle over the covering sample range plus the Lipschitz bound L / 8192,
-// L = sum_j 2 pi (j+1) |amp_j|. out[k * nb + b]. Cached for the last (template, lattice, edges).
-static const std::vector<double>& tpl_bin_max(const TplDev& T, const std::vector<double>& phi, const double* edges,
-                                              int nb) {
-    static TplDev last;
-    static std::vector<double> lphi, ledg, val;
-    static bool have = false;
-    std::vector<double> edg(edges, edges + nb + 1);
-    if (have && std::memcmp(&last, &T, sizeof(T)) == 0 && lphi == phi && ledg == edg) return val;
-    constexpr int G = 8192;
-    std::vector<double> hs(G);
-    double L = 0.0;
-    for (int j = 0; j < T.K; ++j) L += 2.0 * M_PI * (double)(j + 1) * std::fabs(T.amp[j]);
-    for (int g = 0; g < G; ++g) {
-        double h = 0.0;
-        for (int j = 0; j < T.K; ++j) h += T.amp[j] * std::cos(2.0 * M_PI * (double)(j + 1) * ((double)g / G) + T.loc[j]);
-        hs[(size_t)g] = h;
-    }
-    val.assign(phi.size() * (size_t)nb, 0.0);
-    for (size_t k = 0; k < phi.size(); ++k) {
-        const double sh = phi[k] / (2.0 * M_PI);
-        for (int b = 0; b < nb; ++b) {
-            const int64_t g0 = (int64_t)std::floor((edg[(size_t)b] - sh) * G) - 1;
-            const int64_t g1 = (int64_t)std::ceil((edg[(size_t)b + 1] - sh) * G) + 1;
-            double mx = -INFINITY;
-            for (int64_t g = g0; g <= g1; ++g) mx = std::max(mx, hs[(size_t)(((g % G) + G) % G)]);
-            val[k * (size_t)nb + (size_t)b] = mx + L / G;
-        }
-    }
-    std::memcpy(&last, &T, sizeof(T));
-    lphi = phi;
-    ledg = edg;
-    have = true;
-    return val;
-}
-
-static void tpl_bounds(const TplDev& T, double* hmin, double* hmax) {
-    double lo = 0.0, hi = 0.0;
-    for (int j = 0; j < T.K; ++j) {
-        const double a = std::fabs(T.amp[j]);
-        if (T.model == CRIMP_MODEL_FOURIER) {
-            lo -= a;
-            hi += a;
-        } else if (T.model == CRIMP_MODEL_CAUCHY) {  // a / (cosh w - cos u), cos u in [-1, 1]
-            lo += T.amp[j] / (T.ch[j] + 1.0);
-            hi += T.amp[j] / (T.ch[j] - 1.0);
-        } else {                                     // a exp(k cos u)
-            lo += T.amp[j] * std::exp(-T.kap[j]);
-            hi += T.amp[j] * std::exp(T.kap[j]);
-        }
-    }
-    *hmin = std::min(lo, hi);
-    *hmax = std::max(lo, hi);
-}
-
 extern "C" int crimp_toa_points(const double* x, const int64_t* offsets, int64_t nint, const crimp_template* tpl,
                                 const int64_t* pt_interval, const double* pt_norm, const double* pt_phi, int64_t npts,
                                 double* out, uint32_t flags, void* stream) {
@@ -2354,24 +2352,17 @@ extern "C" int crimp_toa_points(const double* x, const int64_t* offsets, int64_t
     int rc = make_tpl(tpl, &T);
     if (rc) return rc;
     if (npts == 0) return CRIMP_OK;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     // groups of <= 4 consecutive points sharing an interval (host needs the interval ids)
-    std::vector<int64_t> pint((size_t)npts), hoff((size_t)nint + 1);
-    if (dev) {
+    std::vector<int64_t> pint((size_t)npts), hoff;
+    if (dev)
         HIPCHK(d2h(s, pint.data(), pt_interval, npts * sizeof(int64_t)));
-        HIPCHK(d2h(s, hoff.data(), offsets, (nint + 1) * sizeof(int64_t)));
-        HIPCHK(hipStreamSynchronize(s));
-    } else {
+    else
         std::memcpy(pint.data(), pt_interval, npts * sizeof(int64_t));
-        std::memcpy(hoff.data(), offsets, (nint + 1) * sizeof(int64_t));
-    }
-    for (int64_t i = 0; i < nint; ++i) ARGCHK(hoff[i + 1] >= hoff[i] && hoff[i] >= 0, "offsets must be non-decreasing");
+    rc = read_offsets(call, offsets, nint, false, "offsets must be non-decreasing", &hoff);
+    if (rc) return rc;
     std::vector<int64_t> gint, gfirst;
     std::vector<int32_t> gnp;
     for (int64_t p = 0; p < npts;) {
@@ -2413,31 +2404,10 @@ extern "C" int crimp_toa_points(const double* x, const int64_t* offsets, int64_t
     return finish(s, flags);
 }
 
-// k_toa_grid_mf's power-of-two coefficient scale: 0 when the largest |amp_j| is in [1, 4096], otherwise the exponent
-// that brings it there; *ok = false where even that is out of reach (the exponent is clamped to [-64, 20], so that
-// s x 500 stays far from fp32 overflow in the kernel's products of four factors): those go to the VALU kernel.
-static int grid_mf_scale(const TplDev& T, bool* ok) {
-    double m = 0.0;
-    for (int j = 0; j < T.K; ++j) m = std::max(m, std::fabs(T.amp[j]));
-    *ok = std::isfinite(m) && m > 0.0;
-    if (!*ok) return 0;
-    int e = 0;
-    while (std::ldexp(m, e) < 1.0 && e < 20) ++e;
-    while (std::ldexp(m, e) > 4096.0 && e > -64) --e;
-    const double ms = std::ldexp(m, e);
-    *ok = ms >= 1.0 && ms <= 4096.0;
-    return e;
-}
-
 // Per-split brute-grid partial sums (k_toa_grid) for nint <= 65535 intervals of at most maxn photons:
 // pl[((split*nint + i)*nnorm + a)*nphi + b] (log2 sums), ph[(split*nint + i)*nphi + b] (min h).
-// mode (crimp_toa_fit's brute grid, Fourier templates on k_toa_grid_mf only): bit 0 (kGridNoMin) -- no per-phShift
-// min h (*ph = nullptr: the host's template bound certifies every candidate norm + h > 0); bit 1 (kGridProd8) -- log2 of
-// products of eight model values (the host certified that every factor of a valid lattice point stays inside
-// [2^-15, 2^15] after the coefficient scale, or k_toa_grid_best checks it where the min decides validity)
-// bit 2 (kGridCert) -- no per-phShift min either: the lazy norms' points are shown invalid by the phase histogram
-// (k_toa_grid_best with lzmask; crimp_toa_fit_redchi2's histogram, tpl_bin_max)
-constexpr int kGridNoMin = 1, kGridProd8 = 2, kGridCert = 4;
+// mode: crimp_toa_fit's fast brute-grid modes (the kGrid* bits, toa_grid_plan.h; Fourier templates on
+// k_toa_grid_mf only); kGridNoMin and kGridCert leave *ph = nullptr.
 // a_first: the lazy norms [0, a_first) of every interval are not evaluated (their lnsum entries are left unwritten;
 // k_toa_grid_best knows them invalid from the min, or has the grid rerun in full)
 static int toa_grid_partials(Scratch& sc, hipStream_t s, const double* dx, const int64_t* doff, const TplDev* dT,
@@ -2547,11 +2517,6 @@ struct EventGuard {  // an event destroyed on every return path (destruction wai
     }
 };
 
-__global__ __launch_bounds__(64) void k_toa_chi2(const unsigned long long* __restrict__ counts, const TplDev T,
-                                                 const double* __restrict__ expo, const double* __restrict__ rec,
-                                                 const double* __restrict__ centers, int nb, int nfree,
-                                                 double* __restrict__ out);
-
 // CRIMP_TOA_HOST_TRACE=1 (diagnostic): host-side phase times of each crimp_toa_fit(_redchi2) call on stderr
 struct HostTrace {
     bool on;
@@ -2574,6 +2539,167 @@ struct HostTrace {
     }
 };
 
+// measureToAs.py:715-725 / :757-771 (readvaryparam=False) and :320-376
+static FitCfg toa_fit_cfg(const crimp_template* tpl, const TplDev& T, double norm0, int32_t ph_shift_res,
+                          const ToaHooks& hooks) {
+    FitCfg C;
+    C.lo = norm0 / 100.0;
+    C.hi = 500.0;
+    C.pb = T.model == CRIMP_MODEL_FOURIER ? M_PI : 1.5 * M_PI;
+    C.step = (2.0 * M_PI) / (double)ph_shift_res;
+    C.kcap = (double)ph_shift_res / 2.0;
+    C.sum_amp = 0.0;
+    for (int j = 0; j < tpl->ncomp; ++j) C.sum_amp += tpl->amp[j] * tpl->amp_shift;
+    C.amp_lo = T.model == CRIMP_MODEL_FOURIER ? 0.01 : 0.0;                                  // :308, :461, :605
+    C.amp_hi = T.model == CRIMP_MODEL_FOURIER ? 100.0 : T.model == CRIMP_MODEL_CAUCHY ? INFINITY : 500.0;
+    C.mom_r = hooks.has_mom_r ? hooks.mom_r : kMomR;
+    return C;
+}
+
+// The launches of one crimp_toa_fit call over its staged inputs and uploaded plan, on the caller's stream
+struct ToaFitRun {
+    Scratch& sc;
+    hipStream_t s;
+    bool timed;
+    const TplDev& T;
+    const FitCfg& C;
+    const std::vector<int64_t>& hoff;
+    int64_t nint;
+    const GridPlan* plan;    // nullptr: no brute grid
+    const EventGuard& ebin;  // the auxiliary stream's histogram has finished (kGridCert reads its counts)
+    int lattice_start = 0;
+    bool vary_amps = false;
+    int nbins = 0;
+    const double *dx = nullptr, *de = nullptr;
+    const int64_t* doff = nullptr;
+    TplDev* dT = nullptr;
+    double *dout = nullptr, *dstart = nullptr, *dphi = nullptr, *dnrm = nullptr;
+    double* hcache = nullptr;  // per-photon template part for the iterative norm profiles of the 1-sigma scan (only
+                               // the CRIMP_FIT_MOMENTS=0 build caches it; the moment profile needs none)
+    int* dunsafe = nullptr;    // k_toa_grid_best: a valid lattice point whose min factor is below 2^-15 / s, or of a
+                               // lazy norm
+    uint64_t* dlzmask = nullptr;
+    int* dlzrow = nullptr;
+    unsigned long long* dcnt = nullptr;
+
+    // the plan's tables through the page-locked staging buffer, and the cleared unsafe flag
+    int upload_plan() {
+        const GridPlan& P = *plan;
+        HIPCHK(sc.alloc(&dphi, P.phi.size()));
+        HIPCHK(sc.alloc(&dnrm, P.nrm.size()));
+        HIPCHK(h2d_async(s, dphi, P.phi.data(), P.phi.size() * sizeof(double)));
+        HIPCHK(h2d_async(s, dnrm, P.nrm.data(), P.nrm.size() * sizeof(double)));
+        if (P.mode & kGridCert) {
+            HIPCHK(sc.alloc(&dlzmask, P.mask.size()));
+            HIPCHK(sc.alloc(&dlzrow, P.row.size()));
+            HIPCHK(h2d_async(s, dlzmask, P.mask.data(), P.mask.size() * sizeof(uint64_t)));
+            HIPCHK(h2d_async(s, dlzrow, P.row.data(), P.row.size() * sizeof(int)));
+        }
+        HIPCHK(sc.alloc(&dunsafe, 1));
+        HIPCHK(hipMemsetAsync(dunsafe, 0, sizeof(int), s));
+        return CRIMP_OK;
+    }
+
+    // brute grid of every interval (k_toa_grid_mf / k_toa_grid + k_toa_grid_best)
+    int brute(int md) {
+        const GridPlan& P = *plan;
+        const int64_t nc = P.nc, nphi = (int64_t)P.phi.size();
+        for (int64_t i0 = 0; i0 < nint; i0 += 65535) {
+            const int64_t nb = std::min<int64_t>(65535, nint - i0);
+            int64_t maxn = 0;
+            for (int64_t i = i0; i < i0 + nb; ++i) maxn = std::max(maxn, hoff[i + 1] - hoff[i]);
+            double *pl = nullptr, *ph = nullptr;
+            int64_t splits = 0;
+            int ran = 0;
+            const int64_t lz = (md & kGridProd8) ? P.nlazy : 0;
+            const int r2 = toa_grid_partials(sc, s, dx, doff + i0, dT, T, dnrm + i0 * nc, nc, dphi, nphi, nb, maxn, &pl,
+                                             &ph, &splits, md, &ran, lz);
+            if (r2) return r2;
+            g_last_grid_fast = ran;
+            g_last_grid_norms = nc - ((ran & kGridProd8) ? lz : 0);  // the lazy norms are not evaluated
+            const bool cert = ran & kGridCert;
+            if (cert && ebin.e) HIPCHK(hipStreamWaitEvent(s, ebin.e, 0));  // the histogram's counts
+            k_toa_grid_best<<<(unsigned)nb, 256, 0, s>>>(pl, ph, dnrm + i0 * nc, dphi, doff + i0, de + i0, (int)nc,
+                                                        (int)nphi, (int)nb, (int)splits, T.model, C.sum_amp,
+                                                        P.grid_n[0], C.lo, C.hi, lattice_start, P.hb,
+                                                        (ran & kGridProd8) ? P.gsc : 0.0,
+                                                        (ran & kGridProd8) ? (int)lz : 0, dunsafe,
+                                                        cert ? dlzmask : nullptr, cert ? dlzrow + i0 * lz : nullptr,
+                                                        cert ? dcnt + i0 * nbins : nullptr, cert ? nbins : 0,
+                                                        dstart + 2 * i0);
+            HIPCHK(hipGetLastError());
+        }
+        return CRIMP_OK;
+    }
+
+    // the fit kernel over every interval
+    void fit() {
+        if (vary_amps) {
+            k_toa_fit_amp<<<(unsigned)nint, kFitBlock, 0, s>>>(dx, doff, dT, de, dstart, C, dout);
+            return;
+        }
+#define CRIMP_LF(MD, KK) k_toa_fit<MD, KK><<<(unsigned)nint, kFitBlock, 0, s>>>(dx, doff, dT, de, dstart, C, dout, hcache)
+        if (T.model == CRIMP_MODEL_FOURIER) {
+            switch (T.K) {  // the template size at compile time (0: read at run time)
+                case 1: CRIMP_LF(CRIMP_MODEL_FOURIER, 1); break;
+                case 2: CRIMP_LF(CRIMP_MODEL_FOURIER, 2); break;
+                case 3: CRIMP_LF(CRIMP_MODEL_FOURIER, 3); break;
+                case 4: CRIMP_LF(CRIMP_MODEL_FOURIER, 4); break;
+                case 5: CRIMP_LF(CRIMP_MODEL_FOURIER, 5); break;
+                case 6: CRIMP_LF(CRIMP_MODEL_FOURIER, 6); break;
+                case 7: CRIMP_LF(CRIMP_MODEL_FOURIER, 7); break;
+                case 8: CRIMP_LF(CRIMP_MODEL_FOURIER, 8); break;
+                default: CRIMP_LF(CRIMP_MODEL_FOURIER, 0); break;
+            }
+        } else if (T.model == CRIMP_MODEL_CAUCHY) {
+            CRIMP_LF(CRIMP_MODEL_CAUCHY, 0);
+        } else {
+            CRIMP_LF(CRIMP_MODEL_VONMISES, 0);
+        }
+#undef CRIMP_LF
+    }
+
+    // Brute grid, then fits, in sequence on the caller's stream. Measured, rejected and removed: the intervals in two
+    // halves on two streams, the second half's grid beside the first half's fits (config 5: 6.1 vs 5.7 ms per 1250
+    // intervals, profiles/r04/toa_breakdown.log) -- each half's fit runs 1.2 rounds of the resident workgroups and its
+    // grid half as many blocks, so the tails grow, not shrink
+    int all(int md) {
+        KernelTimer kg(s, timed);  // brute grid: k_toa_grid(_mf) + k_toa_grid_best
+        kg.start();
+        if (plan) {
+            const int r2 = brute(md);
+            if (r2) return r2;
+            kg.stop();
+        }
+        KernelTimer kf(s, timed);  // the fit kernel
+        kf.start();
+        fit();
+        HIPCHK(hipGetLastError());
+        kf.stop();
+        return CRIMP_OK;
+    }
+};
+
+// redChi2's histogram on the auxiliary stream, beside the grid and the fits; *ebin marks its end
+static int toa_hist_aux(hipStream_t s, const double* dx, const int64_t* doff, const double* dedg, int nbins, int64_t nint,
+                        int64_t ntot, unsigned long long* dcnt, EventGuard* ebin) {
+    hipStream_t s1 = aux_stream();
+    if (!s1) return set_err(CRIMP_ERR_HIP, "cannot create the auxiliary stream");
+    EventGuard e0;
+    HIPCHK(hipEventCreateWithFlags(&e0.e, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(e0.e, s));
+    HIPCHK(hipStreamWaitEvent(s1, e0.e, 0));
+    k_binphases<<<dim3((unsigned)nint, (unsigned)bin_splits(ntot, nint)), 64 * kBinWaves, 0, s1>>>(dx, doff, dedg, nbins,
+                                                                                                  dcnt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventCreateWithFlags(&ebin->e, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ebin->e, s1));
+    return CRIMP_OK;
+}
+
+// crimp_toa_fit(_redchi2): the inputs staged, the brute grid planned on the host (plan_brute_grid) and its tables
+// uploaded, the grid and the fits launched (ToaFitRun), rerun with the full kernel where a runtime certificate failed,
+// then redChi2 from the final records
 static int toa_fit_impl(const double* x, const int64_t* offsets, int64_t nint, const crimp_template* tpl,
                         const double* exposure, double norm0, int32_t ph_shift_res, int32_t options, double* out,
                         uint32_t flags, void* stream, const RedChi2Req* rq) {
@@ -2585,398 +2711,108 @@ static int toa_fit_impl(const double* x, const int64_t* offsets, int64_t nint, c
     TplDev T;
     int rc = make_tpl(tpl, &T);
     if (rc) return rc;
-    const bool brutemin = options & CRIMP_TOA_BRUTE, vary_amps = options & CRIMP_TOA_VARY_AMPS;
+    const bool brutemin = options & CRIMP_TOA_BRUTE;
     if (brutemin) ARGCHK(T.K <= kGridKMax, "brute grid supports at most 8 template components");
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    const ToaHooks hooks = ToaHooks::from_env();
     HostTrace ht;
     g_last_grid_norms = 0;
     g_last_grid_fast = 0;
     // the host's copies of the offsets, exposures and (crimp_toa_fit_redchi2) histogram edges: one stream drain for all
     std::vector<int64_t> hoff((size_t)nint + 1);
-    std::vector<double> hexp0((size_t)nint), hedg0(rq ? (size_t)rq->nbins + 1 : 0);
-    pin_begin((size_t)65536 + (size_t)nint * 340 + hedg0.size() * 8);
-    if (dev) {
-        const size_t bo = (nint + 1) * sizeof(int64_t), be = nint * sizeof(double), bg = hedg0.size() * sizeof(double);
-        const size_t need = ((bo + 255) & ~size_t(255)) + ((be + 255) & ~size_t(255)) + ((bg + 255) & ~size_t(255));
-        if (g_pin.p && need <= g_pin.cap) {  // three async reads into the staging buffer, one drain
-            char* q = g_pin.p;
-            HIPCHK(hipMemcpyAsync(q, offsets, bo, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(q + ((bo + 255) & ~size_t(255)), exposure, be, hipMemcpyDeviceToHost, s));
-            if (rq)
-                HIPCHK(hipMemcpyAsync(q + ((bo + 255) & ~size_t(255)) + ((be + 255) & ~size_t(255)), rq->edges, bg,
-                                      hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            std::memcpy(hoff.data(), q, bo);
-            std::memcpy(hexp0.data(), q + ((bo + 255) & ~size_t(255)), be);
-            if (rq) std::memcpy(hedg0.data(), q + ((bo + 255) & ~size_t(255)) + ((be + 255) & ~size_t(255)), bg);
-        } else {
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMemcpy(hoff.data(), offsets, bo, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(hexp0.data(), exposure, be, hipMemcpyDeviceToHost));
-            if (rq) HIPCHK(hipMemcpy(hedg0.data(), rq->edges, bg, hipMemcpyDeviceToHost));
-        }
-    } else {
-        std::memcpy(hoff.data(), offsets, (nint + 1) * sizeof(int64_t));
-        std::memcpy(hexp0.data(), exposure, nint * sizeof(double));
-        if (rq) std::memcpy(hedg0.data(), rq->edges, hedg0.size() * sizeof(double));
-    }
-    for (int64_t i = 0; i < nint; ++i)
-        ARGCHK(hoff[i + 1] > hoff[i] && hoff[i] >= 0,
-               "every ToA interval needs photons (measureToAs.py:182 fails on an empty one)");
+    std::vector<double> hexp((size_t)nint), hedg(rq ? (size_t)rq->nbins + 1 : 0);
+    pin_begin((size_t)65536 + (size_t)nint * 340 + hedg.size() * 8);
+    HIPCHK(read_list(call, {{hoff.data(), offsets, hoff.size() * sizeof(int64_t)},
+                            {hexp.data(), exposure, hexp.size() * sizeof(double)},
+                            {hedg.data(), rq ? rq->edges : nullptr, hedg.size() * sizeof(double)}}));
+    rc = check_offsets(hoff, true, "every ToA interval needs photons (measureToAs.py:182 fails on an empty one)");
+    if (rc) return rc;
     g_pin.used = 0;  // the reads are in the host's vectors: the staging buffer starts over for the uploads
     ht.mark("offsets");
-    // measureToAs.py:715-725 / :757-771 (readvaryparam=False) and :320-376
-    FitCfg C;
-    C.lo = norm0 / 100.0;
-    C.hi = 500.0;
-    C.pb = T.model == CRIMP_MODEL_FOURIER ? M_PI : 1.5 * M_PI;
-    C.step = (2.0 * M_PI) / (double)ph_shift_res;
-    C.kcap = (double)ph_shift_res / 2.0;
-    C.sum_amp = 0.0;
-    for (int j = 0; j < tpl->ncomp; ++j) C.sum_amp += tpl->amp[j] * tpl->amp_shift;
-    C.amp_lo = T.model == CRIMP_MODEL_FOURIER ? 0.01 : 0.0;                                  // :308, :461, :605
-    C.amp_hi = T.model == CRIMP_MODEL_FOURIER ? 100.0 : T.model == CRIMP_MODEL_CAUCHY ? INFINITY : 500.0;
-    C.mom_r = kMomR;
-    if (const char* e = getenv("CRIMP_FIT_MOM_R")) C.mom_r = atof(e);  // test hook: 0 = iterative norm profiles
+    const FitCfg C = toa_fit_cfg(tpl, T, norm0, ph_shift_res, hooks);
     {
         Scratch sc(s);
-        const double *dx = nullptr, *de = nullptr;
-        const int64_t* doff = nullptr;
-        double* dout = nullptr;
-        HIPCHK(stage_in(sc, x, (size_t)hoff[nint], dev, &dx));
-        HIPCHK(stage_in(sc, offsets, (size_t)nint + 1, dev, &doff));
-        HIPCHK(stage_in(sc, exposure, (size_t)nint, dev, &de));
-        HIPCHK(stage_out(sc, out, (size_t)nint * 8, dev, &dout));
+        // destroyed before sc releases its blocks: on an error return between the histogram's launch on the
+        // auxiliary stream and the caller stream's wait for it, dcnt stays held until the histogram has finished
+        EventGuard ebin;
+        ebin.wait = true;
+        GridPlan plan;
+        ToaFitRun R{sc, s, call.timed, T, C, hoff, nint, brutemin ? &plan : nullptr, ebin};
+        R.lattice_start = hooks.lattice_start;
+        R.vary_amps = options & CRIMP_TOA_VARY_AMPS;
+        HIPCHK(stage_in(sc, x, (size_t)hoff[nint], dev, &R.dx));
+        HIPCHK(stage_in(sc, offsets, (size_t)nint + 1, dev, &R.doff));
+        HIPCHK(stage_in(sc, exposure, (size_t)nint, dev, &R.de));
+        HIPCHK(stage_out(sc, out, (size_t)nint * 8, dev, &R.dout));
         // redChi2's histogram (crimp_toa_fit_redchi2) needs only the photons: it runs on the auxiliary stream beside
         // the brute grid and the fits, in the partly empty last round of the fit's workgroups (timed calls: on this
         // stream before the grid's timer starts, so that the kernel times stay those of the grid and the fit alone).
         // The brute grid's lazy-norm certificate reads it too (kGridCert).
         const double *dedg = nullptr, *dcen = nullptr;
         double* dred = nullptr;
-        unsigned long long* dcnt = nullptr;
-        // destroyed before sc releases its blocks: on an error return between the histogram's launch on the
-        // auxiliary stream and the caller stream's wait for it, dcnt stays held until the histogram has finished
-        EventGuard ebin;
-        ebin.wait = true;
-        bool hist_pending = false;
         if (rq) {
+            R.nbins = rq->nbins;
             HIPCHK(stage_in(sc, rq->edges, (size_t)rq->nbins + 1, dev, &dedg));
             HIPCHK(stage_in(sc, rq->centers, (size_t)rq->nbins, dev, &dcen));
             HIPCHK(stage_out(sc, rq->out, (size_t)nint, dev, &dred));
-            HIPCHK(sc.alloc(&dcnt, (size_t)(nint * rq->nbins)));
-            HIPCHK(hipMemsetAsync(dcnt, 0, (size_t)(nint * rq->nbins) * sizeof(unsigned long long), s));
-            if (!(flags & CRIMP_FLAG_TIME_KERNELS)) {
-                // launched by launch_hist() once the grid's uploads are queued: launched here, its blocks held every
-                // CU while the uploads' copy kernels waited for one (the grid started ~180 us late, rocprofv3 trace)
-                hist_pending = true;
-            } else {
+            HIPCHK(sc.alloc(&R.dcnt, (size_t)(nint * rq->nbins)));
+            HIPCHK(hipMemsetAsync(R.dcnt, 0, (size_t)(nint * rq->nbins) * sizeof(unsigned long long), s));
+            if (call.timed) {
                 k_binphases<<<dim3((unsigned)nint, (unsigned)bin_splits(hoff[nint], nint)), 64 * kBinWaves, 0, s>>>(
-                    dx, doff, dedg, rq->nbins, dcnt);
+                    R.dx, R.doff, dedg, rq->nbins, R.dcnt);
                 HIPCHK(hipGetLastError());
             }
         }
         ht.mark("stage+hist");
-        TplDev* dT = nullptr;
-        double* dstart = nullptr;
-        HIPCHK(sc.alloc(&dT, 1));
-        HIPCHK(h2d_async(s, dT, &T, sizeof(T)));
-        HIPCHK(sc.alloc(&dstart, (size_t)(2 * nint)));
-        std::vector<double> hphi, hnrm, hstart, grid_n;
-        // the brute grid's state, used by the launches below the setup (run_brute)
-        int64_t nphi = 0, nc = 0, nlazy = 0;
-        double hb = 0.0, gsc = 1.0;
-        int grid_mode = 0, lattice_start = 0;
-        double *dphi = nullptr, *dnrm = nullptr;
-        int* dunsafe = nullptr;
-        uint64_t* dlzmask = nullptr;
-        int* dlzrow = nullptr;
-        std::function<int(int, hipStream_t, int64_t, int64_t)> run_brute;
+        HIPCHK(sc.alloc(&R.dT, 1));
+        HIPCHK(h2d_async(s, R.dT, &T, sizeof(T)));
+        HIPCHK(sc.alloc(&R.dstart, (size_t)(2 * nint)));
+        std::vector<double> hstart;
         if (brutemin) {
-            // lmfit brute lattices (measureToAs.py:292-295): scipy mgrid phShift = k*0.05 - bound, 20 norms
-            nphi = (int64_t)std::ceil((2.0 * C.pb) / (0.05 * 1.0));
-            const int64_t nn = 20;
-            hphi.resize((size_t)nphi);
-            for (int64_t k = 0; k < nphi; ++k) hphi[(size_t)k] = (double)k * 0.05 + (-C.pb);
-            grid_n.resize((size_t)nn);
-            for (int64_t a = 0; a < nn; ++a) grid_n[(size_t)a] = (double)a * ((C.hi - C.lo) / (double)(nn - 1)) + C.lo;
-            // Pruned norm axis. At fixed phShift the extended LL is -nE + sum_i ln(n + h_i) + const (every model:
-            // templatemodels.py:109-121, :213-226, :318-329), strictly concave in n, with its maximum n* where
-            // sum_i 1/(n* + h_i) = E, so n* lies in [N/E - hmax, N/E - hmin] for any bounds hmin <= h_i <= hmax. The
-            // lattice maximum over the norms at that phShift is then at one of the grid norms adjacent to that
-            // interval: every other grid norm is strictly lower (a whole grid step, ~26 norm units, from a
-            // bracketing one), so the brute grid's argmax (lmfit brute, measureToAs.py:292-295) is found among them.
-            // Config 5 and the worked example: 2 of the 20 norms.
-            double hlo = 0.0, hhi = 0.0;
-            tpl_bounds(T, &hlo, &hhi);
-            const std::vector<double>& hexp = hexp0;
-            std::vector<int64_t> alo((size_t)nint), acnt((size_t)nint);
-            int64_t ncand = 1;
-            for (int64_t i = 0; i < nint; ++i) {
-                const double r = (double)(hoff[i + 1] - hoff[i]) / hexp[(size_t)i];
-                const double lo_n = r - hhi, hi_n = r - hlo, eps = 1e-9 * (1.0 + std::fabs(r) + hhi - hlo);
-                int64_t a0 = 0, a1 = nn - 1;
-                if (std::isfinite(lo_n) && std::isfinite(hi_n) && hexp[(size_t)i] > 0.0) {
-                    while (a0 + 1 < nn && grid_n[(size_t)(a0 + 1)] <= lo_n - eps) ++a0;
-                    while (a1 > a0 && grid_n[(size_t)(a1 - 1)] >= hi_n + eps) --a1;
-                }
-                alo[(size_t)i] = a0;
-                acnt[(size_t)i] = a1 - a0 + 1;
-                ncand = std::max(ncand, a1 - a0 + 1);
-            }
-            if (ncand > kGridNNSmall || getenv("CRIMP_TOA_FULL_GRID")) {  // (test hook: evaluate all 20 norms)
-                for (int64_t i = 0; i < nint; ++i) {
-                    alo[(size_t)i] = 0;
-                    acnt[(size_t)i] = nn;
-                }
-                ncand = nn;
-            }
-            // compacted per-interval norms: the candidates in grid order, padded by repeating the last (a repeat
-            // comes later in norm-outer order, so it never wins a tie)
-            nc = ncand <= 2 ? 2 : ncand <= kGridNNSmall ? kGridNNSmall : ncand;
-            g_last_grid_norms = nc;
-            hnrm.resize((size_t)(nint * nc));
-            for (int64_t i = 0; i < nint; ++i)
-                for (int64_t c = 0; c < nc; ++c)
-                    hnrm[(size_t)(i * nc + c)] = grid_n[(size_t)(alo[(size_t)i] + std::min(c, acnt[(size_t)i] - 1))];
-            HIPCHK(sc.alloc(&dphi, (size_t)nphi));
-            HIPCHK(sc.alloc(&dnrm, (size_t)(nint * nc)));
-            HIPCHK(h2d_async(s, dphi, hphi.data(), nphi * sizeof(double)));
-            HIPCHK(h2d_async(s, dnrm, hnrm.data(), nint * nc * sizeof(double)));
-            // test hook: start the ascent at the brute lattice point itself (not at the rate norm + parabola vertex)
-            lattice_start = getenv("CRIMP_TOA_LATTICE_START") != nullptr;
-            // Fast brute grid (k_toa_grid_mf, Fourier): without the per-phShift min h when a lower bound hb of h keeps
-            // every candidate lattice point valid (norm + h > 0) and decides k_toa_grid_best's start rule as the min
-            // would (hb + N/E > N/E / 2 for every interval); with log2 of products of eight model values when every
-            // factor s (norm + h) of a valid point stays in [2^-15, 2^15], so that a product of eight is a normal fp32:
-            // certified here from hb and the template's upper bound for the norms above -hb, and checked by
-            // k_toa_grid_best (from the min) for the others -- a lattice point there that could have underflowed sends
-            // the grid back to the four-factor kernel (test hook CRIMP_TOA_GRID_SLOW: always the full kernel).
-            hb = tpl_hmin_scan(T);
-            int mode = 0;
-            bool mf_ok = false;
-            gsc = std::ldexp(1.0, grid_mf_scale(T, &mf_ok));
-            // the fast modes exist on k_toa_grid_mf only (toa_grid_partials' own test): decided once here, so that
-            // a Cauchy / von Mises / K > kGridKMax fit sets up no mode state, certificate or unsafe readback
-            const bool mf_grid = T.model == CRIMP_MODEL_FOURIER && CRIMP_GRID_MFMA && T.K <= kGridKMax && mf_ok;
-            if (mf_grid && getenv("CRIMP_TOA_GRID_SLOW") == nullptr && std::isfinite(hb)) {
-                bool nomin = true, prod8 = true;
-                for (const double nv : hnrm) {
-                    nomin = nomin && nv + hb > 0.0;
-                    prod8 = prod8 && (nv + hhi) * gsc <= std::ldexp(1.0, 15) &&
-                            (nv + hb <= 0.0 || (nv + hb) * gsc >= std::ldexp(1.0, -15));
-                }
-                for (int64_t i = 0; i < nint && nomin; ++i) {
-                    const double r = (double)(hoff[i + 1] - hoff[i]) / hexp[(size_t)i];
-                    nomin = hb + r > 0.5 * r;
-                }
-                mode = (nomin ? kGridNoMin : 0) | (prod8 ? kGridProd8 : 0);
-            }
-            // Lazy norms: the leading candidate norms of every interval with norm + hb <= 0 are left out of the grid.
-            // Their lattice points are valid only where the per-phShift min h exceeds -norm; k_toa_grid_best marks the
-            // rest -inf, as the full grid does, and a valid one sends the grid back to the full evaluation. (Config 5:
-            // lmfit's lowest grid norm, norm0/100, is a candidate of every interval and invalid everywhere.)
-            // lazy_uniform: every interval has exactly nlazy leading lazy norms. The certificate below needs it: an
-            // interval with more would have evaluated norms with norm + hb <= 0 that k_toa_grid_best, without the min,
-            // could not judge.
-            bool lazy_uniform = false;
-            if ((mode & kGridProd8) && !(mode & kGridNoMin)) {
-                nlazy = nc;
-                int64_t zmax = 0;
-                for (int64_t i = 0; i < nint; ++i) {
-                    int64_t z = 0;
-                    while (z < nc && hnrm[(size_t)(i * nc + z)] + hb <= 0.0) ++z;
-                    nlazy = std::min(nlazy, z);
-                    zmax = std::max(zmax, z);
-                }
-                lazy_uniform = zmax == nlazy;
-                if (nlazy >= nc) nlazy = 0;  // every candidate lazy: evaluate them all
-            }
-            // Lazy-norm certificate (crimp_toa_fit_redchi2, whose histogram is at hand; CRIMP_TOA_NO_CERT: off): a lazy
-            // point (norm n0, phi_k) is invalid when some photon has h <= -n0; it does where a bin b holds photons and
-            // the template's bound over that bin at phi_k (tpl_bin_max) is <= -n0 - margin (1e-3 + 1e-5 of the
-            // amplitude sum and n0: it covers the kernel's fp32 h). With the start rule decided by hb too (as kGridNoMin), the grid then needs no min h:
-            // k_toa_grid_best marks those points -inf from the counts, and one it cannot show invalid reruns the grid
-            // with the min (the flag below). Used only when every (lazy norm, phi_k) has such a bin.
-            if (rq && nlazy > 0 && lazy_uniform && mode == kGridProd8 && rq->nbins <= 64 &&
-                getenv("CRIMP_TOA_NO_CERT") == nullptr) {
-                bool srule = true;
-                for (int64_t i = 0; i < nint && srule; ++i) {
-                    const double r = (double)(hoff[i + 1] - hoff[i]) / hexp[(size_t)i];
-                    srule = hb + r > 0.5 * r;
-                }
-                if (srule) {
-                    const int nb = rq->nbins;
-                    const std::vector<double>& hedg = hedg0;
-                    const std::vector<double>& bm = tpl_bin_max(T, hphi, hedg.data(), nb);
-                    std::vector<double> vals;  // the distinct lazy norms (lattice values)
-                    std::vector<int> hrow((size_t)(nint * nlazy));
-                    for (int64_t i = 0; i < nint; ++i)
-                        for (int64_t z = 0; z < nlazy; ++z) {
-                            const double v = hnrm[(size_t)(i * nc + z)];
-                            size_t r = 0;
-                            while (r < vals.size() && vals[r] != v) ++r;
-                            if (r == vals.size()) vals.push_back(v);
-                            hrow[(size_t)(i * nlazy + z)] = (int)r;
-                        }
-                    std::vector<uint64_t> hmask(vals.size() * (size_t)nphi, 0);
-                    // margin over the kernel's h: its f16 hi/lo terms and fp32 sums err by <~ 1e-6 of the amplitude
-                    // sum and of the norm inside the accumulators (k_toa_grid_mf), so 1e-5 of them plus 1e-3
-                    double asum = 0.0;
-                    for (int j = 0; j < T.K; ++j) asum += std::fabs(T.amp[j]);
-                    bool all_k = true;
-                    for (size_t r = 0; r < vals.size(); ++r)
-                        for (int64_t k = 0; k < nphi; ++k) {
-                            const double margin = 1e-3 + 1e-5 * (asum + std::fabs(vals[r]));
-                            uint64_t m = 0;
-                            for (int b = 0; b < nb; ++b)
-                                if (bm[(size_t)k * nb + b] + margin <= -vals[r]) m |= 1ull << b;
-                            hmask[r * (size_t)nphi + (size_t)k] = m;
-                            all_k = all_k && m != 0;
-                        }
-                    if (all_k) {
-                        HIPCHK(sc.alloc(&dlzmask, hmask.size()));
-                        HIPCHK(sc.alloc(&dlzrow, hrow.size()));
-                        HIPCHK(h2d_async(s, dlzmask, hmask.data(), hmask.size() * sizeof(uint64_t)));
-                        HIPCHK(h2d_async(s, dlzrow, hrow.data(), hrow.size() * sizeof(int)));
-                        mode |= kGridCert;
-                    }
-                }
-            }
-            // dunsafe -- k_toa_grid_best: a valid lattice point whose min factor is below 2^-15 / s, or of a lazy norm
-            HIPCHK(sc.alloc(&dunsafe, 1));
-            HIPCHK(hipMemsetAsync(dunsafe, 0, sizeof(int), s));
-            // brute grid of intervals [i0, i0 + n) on stream st (k_toa_grid_mf / k_toa_grid + k_toa_grid_best)
-            auto brute = [&](int md, hipStream_t st, int64_t b0, int64_t bn) -> int {
-                for (int64_t i0 = b0; i0 < b0 + bn; i0 += 65535) {
-                    const int64_t nb = std::min<int64_t>(65535, b0 + bn - i0);
-                    int64_t maxn = 0;
-                    for (int64_t i = i0; i < i0 + nb; ++i) maxn = std::max(maxn, hoff[i + 1] - hoff[i]);
-                    double *pl = nullptr, *ph = nullptr;
-                    int64_t splits = 0;
-                    int ran = 0;
-                    const int64_t lz = (md & kGridProd8) ? nlazy : 0;
-                    const int r2 = toa_grid_partials(sc, st, dx, doff + i0, dT, T, dnrm + i0 * nc, nc, dphi, nphi, nb,
-                                                     maxn, &pl, &ph, &splits, md, &ran, lz);
-                    if (r2) return r2;
-                    g_last_grid_fast = ran;
-                    g_last_grid_norms = nc - ((ran & kGridProd8) ? lz : 0);  // the lazy norms are not evaluated
-                    const bool cert = ran & kGridCert;
-                    if (cert && ebin.e) HIPCHK(hipStreamWaitEvent(st, ebin.e, 0));  // the histogram's counts
-                    k_toa_grid_best<<<(unsigned)nb, 256, 0, st>>>(pl, ph, dnrm + i0 * nc, dphi, doff + i0, de + i0, (int)nc,
-                                                                 (int)nphi, (int)nb, (int)splits, T.model, C.sum_amp,
-                                                                 grid_n[0], C.lo, C.hi, lattice_start, hb,
-                                                                 (ran & kGridProd8) ? gsc : 0.0,
-                                                                 (ran & kGridProd8) ? (int)lz : 0, dunsafe,
-                                                                 cert ? dlzmask : nullptr, cert ? dlzrow + i0 * lz : nullptr,
-                                                                 cert ? dcnt + i0 * rq->nbins : nullptr, cert ? rq->nbins : 0,
-                                                                 dstart + 2 * i0);
-                    HIPCHK(hipGetLastError());
-                }
-                return CRIMP_OK;
-            };
-            grid_mode = mode;
-            run_brute = brute;
+            plan = plan_brute_grid(T, C.lo, C.hi, C.pb, hoff.data(), hexp.data(), nint, rq ? hedg.data() : nullptr,
+                                   rq ? rq->nbins : 0, CRIMP_GRID_MFMA, hooks);
+            g_last_grid_norms = plan.nc;
+            rc = R.upload_plan();
+            if (rc) return rc;
         } else {  // Nelder-Mead starts from the template (norm0, phShift 0) (measureToAs.py:301)
             hstart.resize((size_t)(2 * nint));
             for (int64_t i = 0; i < nint; ++i) {
                 hstart[(size_t)(2 * i)] = norm0;
                 hstart[(size_t)(2 * i + 1)] = 0.0;
             }
-            HIPCHK(h2d_async(s, dstart, hstart.data(), 2 * nint * sizeof(double)));
+            HIPCHK(h2d_async(s, R.dstart, hstart.data(), 2 * nint * sizeof(double)));
         }
-        // the fit kernel over intervals [f0, f0 + fn) on stream st
-        double* hcache = nullptr;  // per-photon template part for the iterative norm profiles of the 1-sigma scan (only
-                                   // the CRIMP_FIT_MOMENTS=0 build caches it; the moment profile needs none)
-        if (!vary_amps && !CRIMP_FIT_MOMENTS) HIPCHK(sc.alloc(&hcache, (size_t)hoff[nint]));
-        auto fit = [&](hipStream_t st, int64_t f0, int64_t fn) {
-            if (vary_amps) {
-                k_toa_fit_amp<<<(unsigned)fn, kFitBlock, 0, st>>>(dx, doff + f0, dT, de + f0, dstart + 2 * f0, C,
-                                                                  dout + 8 * f0);
-                return;
-            }
-#define CRIMP_LF(MD, KK) k_toa_fit<MD, KK><<<(unsigned)fn, kFitBlock, 0, st>>>(dx, doff + f0, dT, de + f0, dstart + 2 * f0, \
-                                                                             C, dout + 8 * f0, hcache)
-            if (T.model == CRIMP_MODEL_FOURIER) {
-                switch (T.K) {  // the template size at compile time (0: read at run time)
-                    case 1: CRIMP_LF(CRIMP_MODEL_FOURIER, 1); break;
-                    case 2: CRIMP_LF(CRIMP_MODEL_FOURIER, 2); break;
-                    case 3: CRIMP_LF(CRIMP_MODEL_FOURIER, 3); break;
-                    case 4: CRIMP_LF(CRIMP_MODEL_FOURIER, 4); break;
-                    case 5: CRIMP_LF(CRIMP_MODEL_FOURIER, 5); break;
-                    case 6: CRIMP_LF(CRIMP_MODEL_FOURIER, 6); break;
-                    case 7: CRIMP_LF(CRIMP_MODEL_FOURIER, 7); break;
-                    case 8: CRIMP_LF(CRIMP_MODEL_FOURIER, 8); break;
-                    default: CRIMP_LF(CRIMP_MODEL_FOURIER, 0); break;
-                }
-            } else if (T.model == CRIMP_MODEL_CAUCHY) {
-                CRIMP_LF(CRIMP_MODEL_CAUCHY, 0);
-            } else {
-                CRIMP_LF(CRIMP_MODEL_VONMISES, 0);
-            }
-#undef CRIMP_LF
-        };
-        // Brute grid, then fits, in sequence on the caller's stream. Measured, rejected and removed: the intervals in two
-        // halves on two streams, the second half's grid beside the first half's fits (config 5: 6.1 vs 5.7 ms per 1250
-        // intervals, profiles/r04/toa_breakdown.log) -- each half's fit runs 1.2 rounds of the resident workgroups and its
-        // grid half as many blocks, so the tails grow, not shrink
-        auto all = [&](int md) -> int {
-            const bool timed = flags & CRIMP_FLAG_TIME_KERNELS;
-            KernelTimer kg(s, timed);  // brute grid: k_toa_grid(_mf) + k_toa_grid_best
-            kg.start();
-            if (run_brute) {
-                const int r2 = run_brute(md, s, 0, nint);
-                if (r2) return r2;
-            }
-            if (run_brute) kg.stop();
-            KernelTimer kf(s, timed);  // the fit kernel
-            kf.start();
-            fit(s, 0, nint);
-            HIPCHK(hipGetLastError());
-            kf.stop();
-            return CRIMP_OK;
-        };
+        if (!R.vary_amps && !CRIMP_FIT_MOMENTS) HIPCHK(sc.alloc(&R.hcache, (size_t)hoff[nint]));
         ht.mark("setup");
-        if (hist_pending) {  // redChi2's histogram on the auxiliary stream, beside the grid and the fits
-            hipStream_t s1 = aux_stream();
-            if (!s1) return set_err(CRIMP_ERR_HIP, "cannot create the auxiliary stream");
-            EventGuard e0;
-            HIPCHK(hipEventCreateWithFlags(&e0.e, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(e0.e, s));
-            HIPCHK(hipStreamWaitEvent(s1, e0.e, 0));
-            k_binphases<<<dim3((unsigned)nint, (unsigned)bin_splits(hoff[nint], nint)), 64 * kBinWaves, 0, s1>>>(
-                dx, doff, dedg, rq->nbins, dcnt);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventCreateWithFlags(&ebin.e, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ebin.e, s1));
+        if (rq && !call.timed) {
+            // launched here, once the grid's uploads are queued: launched with the staging above, its blocks held every
+            // CU while the uploads' copy kernels waited for one (the grid started ~180 us late, rocprofv3 trace)
+            rc = toa_hist_aux(s, R.dx, R.doff, dedg, rq->nbins, nint, hoff[nint], R.dcnt, &ebin);
+            if (rc) return rc;
         }
-        rc = all(grid_mode);
+        rc = R.all(plan.mode);
         if (rc) return rc;
         ht.mark("launch");
-        if (run_brute && (grid_mode & kGridProd8) && !(grid_mode & kGridNoMin)) {
+        if (brutemin && (plan.mode & kGridProd8) && !(plan.mode & kGridNoMin)) {
             // the runtime half of the certificates (eight factors, lazy norms): a flagged lattice point reruns the
             // grid and the fits with the full four-factor kernel
             int unsafe = 0;
-            HIPCHK(d2h(s, &unsafe, dunsafe, sizeof(int)));
-            HIPCHK(hipStreamSynchronize(s));
+            HIPCHK(d2h(s, &unsafe, R.dunsafe, sizeof(int)));
             if (unsafe) {
-                rc = all(grid_mode & ~(kGridProd8 | kGridCert));
+                rc = R.all(plan.mode & ~(kGridProd8 | kGridCert));
                 if (rc) return rc;
             }
         }
         ht.mark("unsafe");
         if (rq) {  // redChi2 from the final records
             if (ebin.e) HIPCHK(hipStreamWaitEvent(s, ebin.e, 0));
-            k_toa_chi2<<<(unsigned)nint, 64, 0, s>>>(dcnt, T, de, dout, dcen, rq->nbins, rq->nfree, dred);
+            k_toa_chi2<<<(unsigned)nint, 64, 0, s>>>(R.dcnt, T, R.de, R.dout, dcen, rq->nbins, rq->nfree, dred);
             HIPCHK(hipGetLastError());
             HIPCHK(copy_back(s, rq->out, dred, (size_t)nint, dev));
         }
-        HIPCHK(copy_back(s, out, dout, (size_t)nint * 8, dev));
+        HIPCHK(copy_back(s, out, R.dout, (size_t)nint * 8, dev));
         HIPCHK(hipStreamSynchronize(s));
         ht.mark("chi2+sync");
     }
@@ -3011,25 +2847,13 @@ extern "C" int crimp_toa_grid(const double* x, const int64_t* offsets, int64_t n
     int rc = make_tpl(tpl, &T);
     if (rc) return rc;
     ARGCHK(T.K <= kGridKMax, "brute grid supports at most 8 template components");
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
-    std::vector<int64_t> hoff((size_t)nint + 1);
-    if (dev) {
-        HIPCHK(d2h(s, hoff.data(), offsets, (nint + 1) * sizeof(int64_t)));
-        HIPCHK(hipStreamSynchronize(s));
-    } else {
-        std::memcpy(hoff.data(), offsets, (nint + 1) * sizeof(int64_t));
-    }
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    std::vector<int64_t> hoff;
     int64_t maxn = 0;
-    for (int64_t i = 0; i < nint; ++i) {
-        ARGCHK(hoff[i + 1] >= hoff[i] && hoff[i] >= 0, "offsets must be non-decreasing");
-        maxn = std::max(maxn, hoff[i + 1] - hoff[i]);
-    }
+    rc = read_offsets(call, offsets, nint, false, "offsets must be non-decreasing", &hoff, &maxn);
+    if (rc) return rc;
     {
         Scratch sc(s);
         const double *dx = nullptr, *dnrm = nullptr, *dphi = nullptr;
@@ -3050,7 +2874,6 @@ extern "C" int crimp_toa_grid(const double* x, const int64_t* offsets, int64_t n
         std::vector<double> hl((size_t)(splits * nint * nnorm * nphi)), hh((size_t)(splits * nint * nphi));
         HIPCHK(d2h(s, hl.data(), pl, hl.size() * sizeof(double)));
         HIPCHK(d2h(s, hh.data(), ph, hh.size() * sizeof(double)));
-        HIPCHK(hipStreamSynchronize(s));
         const int64_t L = nint * nnorm * nphi, H = nint * nphi;
         std::vector<double> rl((size_t)L), rh((size_t)H);
         for (int64_t k = 0; k < L; ++k) {
@@ -3090,21 +2913,12 @@ extern "C" int crimp_toa_shape_points(const double* x, const int64_t* offsets, i
         ARGCHK(tpls[p].model >= 0 && tpls[p].model <= 2, "unknown template model");
         ARGCHK(pt_interval[p] >= 0 && pt_interval[p] < nint, "point interval out of range");
     }
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
-    std::vector<int64_t> hoff((size_t)nint + 1);
-    if (dev) {
-        HIPCHK(d2h(s, hoff.data(), offsets, (nint + 1) * sizeof(int64_t)));
-        HIPCHK(hipStreamSynchronize(s));
-    } else {
-        std::memcpy(hoff.data(), offsets, (nint + 1) * sizeof(int64_t));
-    }
-    for (int64_t i = 0; i < nint; ++i) ARGCHK(hoff[i + 1] >= hoff[i] && hoff[i] >= 0, "offsets must be non-decreasing");
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    std::vector<int64_t> hoff;
+    const int rc = read_offsets(call, offsets, nint, false, "offsets must be non-decreasing", &hoff);
+    if (rc) return rc;
     {
         Scratch sc(s);
         const double *dx = nullptr, *dn = nullptr, *dp = nullptr;
@@ -3150,45 +2964,6 @@ extern "C" int crimp_toa_shape_points(const double* x, const int64_t* offsets, i
     return finish(s, flags);
 }
 
-// redChi2 of every fitted interval on the device (measureToAs.py:385-393 and the Cauchy / von Mises copies): against
-// binphases' histogram (k_binphases, np.histogram semantics) the best-fit template curve at the bin centres;
-// chi2 = sum_b (model_b - rate_b)^2 / err_b^2 with rate = cts / (E / nbins), err = sqrt(cts) / (E / nbins) (numpy's
-// division: an empty bin gives inf, or nan where the model is 0 too), summed in bin order, redChi2 = chi2 / (nbins -
-// nfree). One 64-thread block per interval; rec = the fit records (norm [0], phShift [1], ampShift [6]).
-__global__ __launch_bounds__(64) void k_toa_chi2(const unsigned long long* __restrict__ counts, const TplDev T,
-                                                 const double* __restrict__ expo, const double* __restrict__ rec,
-                                                 const double* __restrict__ centers, int nb, int nfree,
-                                                 double* __restrict__ out) {
-    __shared__ double term[256];
-    const int64_t iv = blockIdx.x;
-    const double n = rec[iv * 8], ph = rec[iv * 8 + 1], A = rec[iv * 8 + 6];
-    const double w = expo[iv] / (double)nb;
-    for (int b = threadIdx.x; b < nb; b += 64) {
-        const double xx = centers[b];
-        double y = n;  // toafit.ToAFitter.curve: fourseries / wrapcauchy / vonmises (templatemodels.py:64-82, :166-185,
-                       // :271-290); Fourier by angle subtraction as the host formed it
-        for (int j = 0; j < T.K; ++j) {
-            if (T.model == CRIMP_MODEL_FOURIER) {
-                const double ang = (double)(j + 1) * 2.0 * M_PI * xx + T.loc[j], bph = (double)(j + 1) * ph;
-                y = y + T.amp[j] * A * (cos(ang) * cos(bph) + sin(ang) * sin(bph));
-            } else if (T.model == CRIMP_MODEL_CAUCHY) {
-                y = y + T.amp[j] * A / (T.ch[j] - cos(xx - T.loc[j] - ph));
-            } else {
-                y = y + T.amp[j] * A * exp(T.kap[j] * cos(xx - T.loc[j] - ph));
-            }
-        }
-        const double c = (double)counts[iv * nb + b];
-        const double rate = c / w, err = sqrt(c) / w;
-        term[b] = ((y - rate) * (y - rate)) / (err * err);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double chi2 = 0.0;
-        for (int b = 0; b < nb; ++b) chi2 += term[b];
-        out[iv] = chi2 / (double)(nb - nfree);
-    }
-}
-
 extern "C" int crimp_toa_redchi2(const double* x, const int64_t* offsets, int64_t nint, const crimp_template* tpl,
                                  const double* exposure, const double* records, const double* edges,
                                  const double* centers, int32_t nbins, int32_t nfree, double* out, uint32_t flags,
@@ -3200,20 +2975,14 @@ extern "C" int crimp_toa_redchi2(const double* x, const int64_t* offsets, int64_
     TplDev T;
     int rc = make_tpl(tpl, &T);
     if (rc) return rc;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     int64_t ntot = 0;
-    if (dev) {
+    if (dev)
         HIPCHK(d2h(s, &ntot, offsets + nint, sizeof(int64_t)));
-        HIPCHK(hipStreamSynchronize(s));
-    } else {
+    else
         ntot = offsets[nint];
-    }
     {
         Scratch sc(s);
         const double *dx = nullptr, *de = nullptr, *dc = nullptr, *dexp = nullptr, *drec = nullptr;
@@ -3246,20 +3015,14 @@ extern "C" int crimp_binphases(const double* x, const int64_t* offsets, int64_t 
     ARGCHK(nint >= 1 && nbins >= 1 && nbins <= 256, "bad sizes (nbins must be 1..256)");
     ARGCHK(x != nullptr && offsets != nullptr && edges != nullptr && counts != nullptr, "null argument");
     ARGCHK(nint <= 2147483647LL, "too many intervals");
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     int64_t ntot = 0;
-    if (dev) {
+    if (dev)
         HIPCHK(d2h(s, &ntot, offsets + nint, sizeof(int64_t)));
-        HIPCHK(hipStreamSynchronize(s));
-    } else {
+    else
         ntot = offsets[nint];
-    }
     {
         Scratch sc(s);
         const double *dx = nullptr, *de = nullptr;
@@ -3346,13 +3109,9 @@ extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_m
         D.uni_p = D.uni_p && cube_axis_uniform(e, nph[j]);
         D.it_p = std::max(D.it_p, cube_search_steps(nph[j]));
     }
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     CPModel hm{};
     if (model) make_cpmodel(model, 7, &hm);
     {
@@ -3441,7 +3200,6 @@ static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_mo
     models->resize((size_t)nprob);
     for (int64_t i = 0; i < nprob; ++i) {
         const crimp_timing_model &fm = fit_base[i], &wm = wave_base[i];
-        ARGCHK(h_off[i + 1] > h_off[i], "a problem has no ToAs");
         ARGCHK(h_off[i + 1] - h_off[i] <= (int64_t(1) << 30), "a problem has too many ToAs");
         ARGCHK(fm.n_glitch >= 0 && fm.n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
         ARGCHK(fm.n_wave >= 0 && fm.n_wave <= CRIMP_MAX_WAVE && wm.n_wave >= 0 && wm.n_wave <= CRIMP_MAX_WAVE,
@@ -3464,15 +3222,10 @@ static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_mo
 }
 
 // offsets on the host (the checks and the LDS plan need the ToA counts)
-static int tf_host_offsets(const int64_t* offsets, int64_t nprob, bool dev, hipStream_t s, std::vector<int64_t>* h) {
+static int tf_host_offsets(const Call& c, const int64_t* offsets, int64_t nprob, std::vector<int64_t>* h) {
     ARGCHK(offsets != nullptr && nprob >= 1 && nprob <= (int64_t(1) << 24), "nprob out of range");
-    h->resize((size_t)nprob + 1);
-    if (dev) {
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(h->data(), offsets, h->size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-    } else {
-        std::memcpy(h->data(), offsets, h->size() * sizeof(int64_t));
-    }
+    const int rc = read_offsets(c, offsets, nprob, true, "a problem has no ToAs", h);
+    if (rc) return rc;
     ARGCHK((*h)[0] == 0, "offsets[0] must be 0");
     return CRIMP_OK;
 }
@@ -3483,17 +3236,13 @@ extern "C" int crimp_timing_nll(const double* t_mjd, const double* y, const doub
                                 int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
     ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && pvec != nullptr && nll != nullptr, "null argument");
     ARGCHK(P >= 1 && P <= (int64_t(1) << 24), "P out of range");
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     std::vector<int64_t> h_off;
     std::vector<TFModel> models;
     TFMap dm;
-    int rc = tf_host_offsets(offsets, nprob, dev, s, &h_off);
+    int rc = tf_host_offsets(call, offsets, nprob, &h_off);
     if (rc != CRIMP_OK) return rc;
     rc = tf_prepare(h_off.data(), nprob, fit_base, wave_base, map, &models, &dm);
     if (rc != CRIMP_OK) return rc;
@@ -3542,17 +3291,13 @@ extern "C" int crimp_timing_mcmc(const double* t_mjd, const double* y, const dou
     ARGCHK(W >= 2 && W % 2 == 0 && W <= 256 && W >= 2 * map->ndim, "walkers: even, >= 2 ndim and <= 256");
     ARGCHK(steps >= 1 && steps <= (int64_t(1) << 31), "steps out of range");
     ARGCHK(first_problem >= 0 && first_problem + nprob <= (int64_t(1) << 32), "first_problem out of range");
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     std::vector<int64_t> h_off;
     std::vector<TFModel> models;
     TFMap dm;
-    int rc = tf_host_offsets(offsets, nprob, dev, s, &h_off);
+    int rc = tf_host_offsets(call, offsets, nprob, &h_off);
     if (rc != CRIMP_OK) return rc;
     rc = tf_prepare(h_off.data(), nprob, fit_base, wave_base, map, &models, &dm);
     if (rc != CRIMP_OK) return rc;
@@ -3671,9 +3416,9 @@ extern "C" int crimp_is_sorted(const double* t, int64_t n, int32_t* unsorted, ui
     ARGCHK(unsorted != nullptr && (t != nullptr || n == 0), "null argument");
     *unsorted = 0;
     if (n < 2) return CRIMP_OK;
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream, Call::kKeepTimes);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     {
         Scratch sc(s);
         const double* dt = nullptr;
@@ -3696,9 +3441,9 @@ extern "C" int crimp_select_intervals(const double* t, int64_t n, const double* 
     ARGCHK(n >= 0 && nint >= 0, "negative size");
     ARGCHK((t != nullptr || n == 0) && (nint == 0 || (starts && ends && lo && count)), "null argument");
     if (nint == 0) return CRIMP_OK;
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream, Call::kKeepTimes);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     {
         Scratch sc(s);
         const double *dt = nullptr, *ds = nullptr, *de = nullptr;
@@ -3725,9 +3470,9 @@ extern "C" int crimp_gather_ranges(const double* t, int64_t n, const int64_t* lo
     ARGCHK(nint <= 2147483647LL, "too many intervals");
     ARGCHK(nint == 0 || (t && lo && offsets && out), "null argument");
     if (nint == 0) return CRIMP_OK;
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream, Call::kKeepTimes);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     // the ranges are checked on the host against the photon array before any copy is queued
     std::vector<int64_t> hlo((size_t)nint), hoff((size_t)nint + 1);
     if (dev) {
@@ -3810,13 +3555,9 @@ extern "C" int crimp_sim_events(const crimp_timing_model* model, const crimp_sim
     A.ngti = ngti;
     A.seed = seed;
     A.days = (flags & CRIMP_FLAG_TIME_DAYS) ? 1 : 0;
-    const bool dev = flags & CRIMP_FLAG_DEVICE_PTRS;
-    std::lock_guard<std::mutex> lk(g_mutex);
-    if (flags & CRIMP_FLAG_TIME_KERNELS) {
-        g_kernel_times.clear();
-        g_last_kernel_ms = -1.0;
-    }
-    hipStream_t s = as_stream(stream);
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
     if (ngti > 0) {  // the table is checked on the host before anything is queued
         std::vector<double> hg((size_t)ngti * 2);
         if (dev)
