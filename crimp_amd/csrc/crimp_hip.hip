@@ -916,6 +916,10 @@ __global__ __launch_bounds__(kGridBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         amp[j] = (float)T->amp[j];
                         chj[j] = (float)T->ch[j];
                         kpj[j] = (float)(T->kap[j] * 1.4426950408889634);  // exp(k*cu) = exp2(k*log2e*cu)
+                        // von Mises: a / (2 pi I0(k)) is below fp32's range from k ~ 80 (wid < 0.11) and the whole
+                        // template would read 0: carry a exp(k) / (2 pi I0(k)) = O(a sqrt k) with exp(k (cu - 1))
+                        if (model == CRIMP_MODEL_VONMISES && T->amp[j] != 0.0)
+                            amp[j] = (float)copysign(exp(log(fabs(T->amp[j])) + T->kap[j]), T->amp[j]);
                     }
                 }
             }
@@ -978,7 +982,7 @@ __global__ __launch_bounds__(kGridBlock) __attribute__((amdgpu_waves_per_eu(4)))
                         if (model == CRIMP_MODEL_CAUCHY)
                             h += amp[j] * __builtin_amdgcn_rcpf(chj[j] - cu);
                         else
-                            h += amp[j] * __builtin_amdgcn_exp2f(kpj[j] * cu);
+                            h += amp[j] * __builtin_amdgcn_exp2f(__builtin_fmaf(kpj[j], cu, -kpj[j]));
                     }
                 }
             }
