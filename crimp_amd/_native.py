@@ -88,7 +88,7 @@ class SimShape(ctypes.Structure):
 
 
 EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_last_kernel_times", "crimp_last_fixups",
-           "crimp_last_search_path", "crimp_last_nufft_plan", "crimp_last_nufft_work", "crimp_last_toa_grid_norms", "crimp_last_toa_grid_fast", "crimp_release_scratch",
+           "crimp_last_search_path", "crimp_last_nufft_plan", "crimp_last_nufft_work", "crimp_last_nufft_cells", "crimp_last_toa_grid_norms", "crimp_last_toa_grid_fast", "crimp_release_scratch",
            "crimp_device_count", "crimp_calcphase", "crimp_search", "crimp_search_best", "crimp_best", "crimp_search_sets", "crimp_toa_points",
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
@@ -121,6 +121,7 @@ def load(require_device=True):
             L.crimp_last_kernel_times.argtypes = [ctypes.POINTER(ctypes.c_double), i32]
             L.crimp_last_nufft_plan.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32)]
             L.crimp_last_nufft_work.argtypes = [ctypes.POINTER(ctypes.c_double), i32]
+            L.crimp_last_nufft_cells.argtypes = [ctypes.POINTER(i64), ctypes.POINTER(i64)]
             L.crimp_device_count.argtypes = [ctypes.POINTER(i32)]
             L.crimp_calcphase.argtypes = [P, i64, ctypes.POINTER(TimingModel), i32, P, P, u32, P]
             L.crimp_search.argtypes = [P, i64, ctypes.c_double, P, i64, P, i64, i32, i32, i64, i64, P, u32, P]
@@ -177,6 +178,15 @@ def last_nufft_work():
     L.crimp_last_nufft_work(w, 7)
     return {"spread_flops": w[0], "spread_bytes": w[1], "merge_bytes": w[2], "pass1_bytes": w[3], "pass2_bytes": w[4],
             "combine_bytes": w[5], "finalize_bytes": w[6]}
+
+
+def last_nufft_cells():
+    """(built, reused): the cell-start tables the last NUFFT search built / took from the plan cache
+    (crimp_last_nufft_cells)."""
+    L = load(require_device=False)
+    b, r = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.crimp_last_nufft_cells(ctypes.byref(b), ctypes.byref(r))
+    return int(b.value), int(r.value)
 
 
 NUFFT_CLASSES = ("cellstart", "spread", "merge", "pass1", "pass2", "combine", "finalize")

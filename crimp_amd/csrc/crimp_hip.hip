@@ -2115,6 +2115,12 @@ extern "C" int crimp_last_nufft_plan(int64_t* fft_length, int32_t* moments, int3
     return CRIMP_OK;
 }
 
+extern "C" int crimp_last_nufft_cells(int64_t* built, int64_t* reused) {
+    if (built) *built = g_last_cells_built;
+    if (reused) *reused = g_last_cells_reused;
+    return CRIMP_OK;
+}
+
 extern "C" int crimp_last_nufft_work(double* work, int32_t cap) {
     for (int i = 0; i < kNuCls && i < cap; ++i) work[i] = g_nu_work[i];
     return kNuCls;
@@ -2216,12 +2222,19 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
         // the plan's scalars are recomputed on the device and compared there (k_ap_final), every NUFFT kernel that
         // reads photon-derived tables exits if they differ, and the host, reading the result flags anyway at the
         // end, redoes the search from a fresh plan -- one host round trip per search instead of two.
+        // A cell-gather plan's start tables are kept with it: the repeated search skips the cell-start pass too, and
+        // its gathers check the tables against the photons they read (k_nu_gather, CHECK; the same flag and redo).
         NuSpecKey key{};
         bool spec_mismatch = false;
+        struct CellHold {  // tables built for keeping: released unless the plan cache takes them
+            NuCellTab t;
+            ~CellHold() { nu_cell_release(&t); }
+        } cells;
         if (nu_try && !f64) {
             key = nu_spec_key(dtm, n, t0, dfr, nf, twod ? nfd : 0, nharm, stat, first, count, gather_form);
             NuExpect ex{};
-            if (nu_spec_find(key, nu_hs)) {
+            NuCellTab cached;
+            if (nu_spec_find(key, nu_hs, &cached)) {
                 for (int q = 0; q < 4; ++q) ex.v[q] = nu_hs[q];
                 ex.on = 1;
                 ex.check_order = gather_form ? 0 : 1;
@@ -2231,9 +2244,12 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
                 int64_t nfix = 0;
                 rc = nufft_search(sc, s, dtm, t0, n, dfr, nf, twod ? nfd : 1, dc2, nu_hs, twod, nharm, stat, first,
                                   count, dout, flags & CRIMP_FLAG_TIME_KERNELS, &nfix,
-                                  (flags & CRIMP_FLAG_NO_FIXUP) != 0, &done, best, &best_done, nuflags, &spec_mismatch);
+                                  (flags & CRIMP_FLAG_NO_FIXUP) != 0, &done, best, &best_done, nuflags, &spec_mismatch,
+                                  &cached, &cells.t);
                 if (rc) return rc;
                 if (done) g_last_fixups = nfix;
+                if (done && cells.t.p) nu_spec_attach(key, &cells.t);  // (an entry stored without tables)
+                nu_cell_release(&cells.t);
                 if (spec_mismatch) nu_spec_drop(key);
                 // not done and no mismatch: photons out of order under a still-valid progression (the exact rule)
             }
@@ -2248,11 +2264,12 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
                 bool mm = false;
                 rc = nufft_search(sc, s, dtm, t0, n, dfr, nf, twod ? nfd : 1, dc2, nu_hs, twod, nharm, stat, first,
                                   count, dout, flags & CRIMP_FLAG_TIME_KERNELS, &nfix,
-                                  (flags & CRIMP_FLAG_NO_FIXUP) != 0, &done, best, &best_done, nuflags, &mm);
+                                  (flags & CRIMP_FLAG_NO_FIXUP) != 0, &done, best, &best_done, nuflags, &mm, nullptr,
+                                  &cells.t);
                 if (rc) return rc;
-                if (done) {
+                if (done) {  // ended clean (the order flag read back as 0): the plan and its tables are kept
                     g_last_fixups = nfix;
-                    nu_spec_store(key, nu_hs);
+                    nu_spec_store(key, nu_hs, &cells.t);
                 }
             }
         }

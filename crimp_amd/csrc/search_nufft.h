@@ -466,6 +466,14 @@ __global__ __launch_bounds__(256) void k_nu_cellstart(const double* __restrict__
 // One launch serves up to kNuGatherSet harmonics (NuGatherSet: block ranges, cells, lanes per cell and W plane of
 // each): the harmonics of a search share the launch's waves, so its last round of blocks is not one harmonic's tail
 // (config 3 ran two launches of 1.7 and 3.4 rounds of resident waves).
+// x of the lane a quad_perm DPP control picks inside each quad of lanes (two bits per lane, lane 0's first)
+template <int CTRL>
+__device__ __forceinline__ double nu_quad_perm(double x) {
+    const long long b = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_mov_dpp((int)b, CTRL, 0xF, 0xF, true);
+    const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xF, 0xF, true);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
 constexpr int kNuGatherRows = 2;
 constexpr int kNuGatherSet = 8;
 struct NuGatherSet {
@@ -475,11 +483,19 @@ struct NuGatherSet {
     int64_t gmin[kNuGatherSet], gmax[kNuGatherSet], gbase[kNuGatherSet], gcount[kNuGatherSet];
     int64_t soff[kNuGatherSet], woff[kNuGatherSet];       // the harmonic's start table and W planes
 };
-template <int R, bool TWOD, int PP>  // PP >= P moments accumulated unconditionally (no per-moment selects)
+// CHECK: the start tables are a cached plan's (nu_spec_find), built from the photons an earlier search read. Every
+// lane then verifies what the tables assume of the photons it weights: each sits in the lane's cell G -- the cell
+// k_nu_cellstart forms, (int)rint(k (dt s1)), a product alone, so nothing contracts -- and the photons of a cell do not
+// descend in index order (neighbours through a rotation inside the L-group, checked by the set's first harmonic only:
+// every harmonic's cells hold every photon). The tables partition [0, n), so with every photon in the cell that owns
+// it the sums are those of fresh tables, and the order is the order k_nu_cellstart demands (cells ascend with dt).
+// A failing wave ORs 2 into *bad: the host drops the plan and redoes the search (nufft_search reads the flag first);
+// the kernels after this one then run on W that is wrong but in bounds -- every start lies in [0, n].
+template <int R, bool TWOD, int PP, bool CHECK>  // PP >= P moments accumulated unconditionally (no per-moment selects)
 __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt, double t0,
                                                    const int64_t* __restrict__ startb, int64_t nfft, double s1,
                                                    double fch, double fcl, const double* __restrict__ c2row, int nrow,
-                                                   int P, const NuGatherSet S, const int* __restrict__ bad,
+                                                   int P, const NuGatherSet S, int* __restrict__ bad,
                                                    const double2* __restrict__ tab, double2* __restrict__ Wb) {
     // photons out of order (the cell starts found it): the start tables are not filled (nothing zeroes them), so no
     // lane may read them; the search's results are discarded and the default path runs
@@ -507,6 +523,9 @@ __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt
 #pragma unroll
     for (int r = 0; r < R; ++r) c2[r] = (TWOD && r < nrow) ? c2row[r] : 0.0;
     const double kd = (double)S.k[j];
+    const bool order_check = CHECK && j == 0;  // block-uniform
+    const int lane = threadIdx.x & 63;
+    int fail = 0;
     // the photon times are prefetched raw and unconditionally (indices clamped into the cell, whose stand-ins are
     // never weighted): a load whose value entered a select or a subtraction at its issue would be waited for there;
     // the next cell's photon range is loaded during the current cell
@@ -524,6 +543,8 @@ __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt
         }
         if (i1 <= i0) continue;  // an empty cell (no clamped load below i0)
         const double Gd = (double)G;
+        const int Gi = (int)G;  // cells fit 32 bits (nu_plan)
+        double dlast = 0.0;     // dt of the L-group's last photon of the previous iteration
         // two photons per iteration (independent chains for the VALU; each one's terms still added in photon
         // order), their times prefetched two iterations ahead (HBM latency is several iterations of one wave)
         const int64_t il = i1 - 1;
@@ -538,6 +559,43 @@ __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt
             dn[2] = tt[i + 4 * L < il ? i + 4 * L : il];
             dn[3] = tt[i + 5 * L < il ? i + 5 * L : il];
             const double ea = kd * (da * s1) - Gd, eb = kd * (db * s1) - Gd;
+            if (CHECK) {
+                // |e| clearly below 1/2 settles the cell: the product k (dt s1) the cell-start pass rounds lies within
+                // 2^-23 of the unrounded one e is formed from (|cell| < 2^31), so its rint is G. Else (a cell's edge,
+                // or a photon of another cell) the pass's own expression decides -- dt s1 formed again behind an
+                // empty asm: were that product shared with e, the compiler would no longer fuse it into e's
+                // subtraction, and the moments would differ in the last bits from the fresh plan's
+                constexpr double sure = 0.5 - 0x1p-20;
+                if (!(fabs(ea) < sure && (!hb || fabs(eb) < sure))) {
+                    double ua = da * s1, ub = db * s1;
+                    asm volatile("" : "+v"(ua), "+v"(ub));
+                    fail |= (int)rint(kd * ua) != Gi || (hb && (int)rint(kd * ub) != Gi);
+                }
+                if (order_check) {
+                    // the cell's photons of this iteration in index order: da of lanes 0 .. L-1, then db of lanes
+                    // 0 .. L-1. Every lane hands (da, db) to the next lane of its L-group, the last to lane 0: a
+                    // lane's predecessors are the two it receives, lane 0's are the db of the last lane from the
+                    // previous iteration (kept in dlast) and that lane's da. The L-group runs its cell's iterations
+                    // together, and a received value is used only where the lane it comes from holds a real photon in
+                    // this iteration (a lower index than the user's).
+                    // (the rotation inside pairs and quads is one DPP move per register, no LDS round trip)
+                    double xa = da, xb = db;
+                    if (L == 2) {
+                        xa = nu_quad_perm<0xB1>(da);  // lanes 1 0 3 2
+                        xb = nu_quad_perm<0xB1>(db);
+                    } else if (L == 4) {
+                        xa = nu_quad_perm<0x93>(da);  // lanes 3 0 1 2
+                        xb = nu_quad_perm<0x93>(db);
+                    } else if (L > 4) {
+                        const int from = sub ? lane - 1 : lane | (L - 1);
+                        xa = __shfl(da, from);
+                        xb = __shfl(db, from);
+                    }
+                    const double preva = sub ? xa : dlast, prevb = sub ? xb : xa;
+                    fail |= ((sub || i > i0) && !(preva <= da)) || (hb && !(prevb <= db));
+                    dlast = xb;
+                }
+            }
             const double p1a = nu_frac_prod(fch, fcl, da), p1b = nu_frac_prod(fch, fcl, db);
             double d2a = 0.0, d2ea = 0.0, d2b = 0.0, d2eb = 0.0;
             if (TWOD) {
@@ -577,6 +635,10 @@ __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt
                 }
             }
         }
+    }
+    if (CHECK) {
+        const unsigned long long failed = __ballot(fail);
+        if (failed && lane == __ffsll(failed) - 1) atomicOr(bad, 2);
     }
     for (int o = L / 2; o > 0; o >>= 1)  // block-uniform L
 #pragma unroll
@@ -1641,13 +1703,13 @@ static void nu_launch_spread(int G, dim3 grid, hipStream_t s, const double* tt, 
 }
 
 // Budget of the NUFFT path's device buffers (CRIMP_NUFFT_BUDGET_MB, default 6144): slots, FFT ping-pong, sums.
-template <int R, bool TWOD>
+template <int R, bool TWOD, bool CHECK>
 static void launch_gather_r(int64_t blocks, const double* tt, double t0, const int64_t* start, int64_t nfft, double s1,
                             double fch, double fcl, const double* c2, int nrow, int P, const NuGatherSet& S,
-                            const int* bad, const double2* tab, double2* W, hipStream_t s) {
+                            int* bad, const double2* tab, double2* W, hipStream_t s) {
     const dim3 grid((unsigned)blocks);
 #define NU_GATHER(PPP) \
-    k_nu_gather<R, TWOD, PPP><<<grid, 256, 0, s>>>(tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W)
+    k_nu_gather<R, TWOD, PPP, CHECK><<<grid, 256, 0, s>>>(tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W)
     if (P <= 14) {  // Z^2_m (m >= 2) at config-3-like grids (kNuEpsZm)
         NU_GATHER(14);
     } else if (P <= 15) {
@@ -1661,13 +1723,21 @@ static void launch_gather_r(int64_t blocks, const double* tt, double t0, const i
     }
 #undef NU_GATHER
 }
-static void launch_gather(bool twod, int64_t blocks, const double* tt, double t0, const int64_t* start, int64_t nfft,
-                          double s1, double fch, double fcl, const double* c2, int nrow, int P, const NuGatherSet& S,
-                          const int* bad, const double2* tab, double2* W, hipStream_t s) {
-    if (twod)
-        launch_gather_r<kNuGatherRows, true>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, s);
-    else
-        launch_gather_r<1, false>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, s);
+// check: start is a cached plan's table, validated against the photons by the gather itself (k_nu_gather, CHECK)
+static void launch_gather(bool twod, bool check, int64_t blocks, const double* tt, double t0, const int64_t* start,
+                          int64_t nfft, double s1, double fch, double fcl, const double* c2, int nrow, int P,
+                          const NuGatherSet& S, int* bad, const double2* tab, double2* W, hipStream_t s) {
+#define NU_GATHER_R(RR, TD)                                                                                           \
+    if (check)                                                                                                        \
+        launch_gather_r<RR, TD, true>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, s);     \
+    else                                                                                                              \
+        launch_gather_r<RR, TD, false>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, s)
+    if (twod) {
+        NU_GATHER_R(kNuGatherRows, true);
+    } else {
+        NU_GATHER_R(1, false);
+    }
+#undef NU_GATHER_R
 }
 
 static int64_t nu_cus() {  // compute units of the current device (persistent grids)
@@ -1791,9 +1861,67 @@ struct NuSpecKey {
                gather == o.gather;
     }
 };
+// A cell-gather plan's start tables (k_nu_cellstart), every row group's and harmonic's as nufft_search lays them out,
+// in device memory of the cache's own: built once by a search that ended clean, never written again (every index in
+// them lies in [0, n] whatever the photon buffer holds later) and read by the later searches that find the entry,
+// whose gathers check them against the photons (k_nu_gather, CHECK). Every search returns with its stream drained and
+// calls are serialised (g_mutex), so a table is complete before any later call, on whatever stream, reads it: no
+// event is needed. Memory: at most one allocation per entry (16) plus one spare -- a dropped or evicted entry's
+// allocation becomes the spare, or is freed when there is one already, and a new table takes the spare when it fits.
+// A search that reuses its table allocates and frees nothing.
+struct NuCellTab {
+    int64_t* p = nullptr;
+    int64_t cap = 0, len = 0;  // int64 entries allocated / used (the sum of every group's tables)
+    int dev = 0;               // the device it was allocated on
+};
+static NuCellTab g_nu_cell_spare;
+// tables above this many bytes are rebuilt by every search: 1/32 of the NUFFT's budget, 64 MB at most
+static int64_t nu_cell_cap_bytes() { return std::min<int64_t>(nufft_budget() / 32, int64_t(64) << 20); }
+static bool nu_cell_disabled() {  // CRIMP_NUFFT_CELL_CACHE=0: the plan is reused, its tables are rebuilt (A/B hook)
+    const char* e = getenv("CRIMP_NUFFT_CELL_CACHE");
+    return e && !strcmp(e, "0");
+}
+static void nu_cell_release(NuCellTab* t) {
+    if (t->p) {
+        if (!g_nu_cell_spare.p) {
+            g_nu_cell_spare = *t;
+        } else {
+            (void)hipFree(t->p);
+        }
+    }
+    *t = NuCellTab{};
+}
+// room for len entries (the spare when it fits and is not more than twice too large); false: no memory, no caching
+static bool nu_cell_acquire(NuCellTab* t, int64_t len) {
+    NuCellTab& sp = g_nu_cell_spare;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (sp.p && (sp.dev != dev || sp.cap < len || sp.cap > 2 * len + (int64_t(1) << 17))) {
+        (void)hipFree(sp.p);
+        sp = NuCellTab{};
+    }
+    if (sp.p) {
+        *t = sp;
+        sp = NuCellTab{};
+    } else {
+        void* p = nullptr;
+        if (hipMalloc(&p, (size_t)len * sizeof(int64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        t->p = static_cast<int64_t*>(p);
+        t->cap = len;
+        t->dev = dev;
+    }
+    t->len = len;
+    return true;
+}
+// crimp_last_nufft_cells(): start tables (one per row group and harmonic) the last NUFFT search built / reused
+static int64_t g_last_cells_built = 0, g_last_cells_reused = 0;
 struct NuSpecEntry {
     NuSpecKey key;
     double hs[5];
+    NuCellTab cells;  // none (p == nullptr): an MFMA-slot plan, tables above the cap, or CRIMP_NUFFT_CELL_CACHE=0
 };
 static std::vector<NuSpecEntry> g_nu_spec;
 static bool nu_spec_disabled() {  // CRIMP_NUFFT_PLAN_CACHE=0: every search reads its plan back (A/B hook)
@@ -1817,11 +1945,14 @@ static NuSpecKey nu_spec_key(const double* t, int64_t n, double t0, const double
     (void)hipGetDevice(&k.dev);
     return k;
 }
-static bool nu_spec_find(const NuSpecKey& k, double* hs) {
+// *cells: the entry's start tables (still the entry's own), none where it has none or the cell cache is off
+static bool nu_spec_find(const NuSpecKey& k, double* hs, NuCellTab* cells) {
+    *cells = NuCellTab{};
     if (nu_spec_disabled()) return false;
     for (const NuSpecEntry& e : g_nu_spec)
         if (e.key == k) {
             std::memcpy(hs, e.hs, sizeof(e.hs));
+            if (!nu_cell_disabled()) *cells = e.cells;
             return true;
         }
     return false;
@@ -1829,18 +1960,38 @@ static bool nu_spec_find(const NuSpecKey& k, double* hs) {
 static void nu_spec_drop(const NuSpecKey& k) {
     for (size_t i = 0; i < g_nu_spec.size(); ++i)
         if (g_nu_spec[i].key == k) {
+            nu_cell_release(&g_nu_spec[i].cells);
             g_nu_spec.erase(g_nu_spec.begin() + (std::ptrdiff_t)i);
             return;
         }
 }
-static void nu_spec_store(const NuSpecKey& k, const double* hs) {
-    if (nu_spec_disabled()) return;
+// cells: the tables the search built for keeping (nu_cell_acquire), now the entry's; released where nothing is stored
+static void nu_spec_store(const NuSpecKey& k, const double* hs, NuCellTab* cells) {
+    if (nu_spec_disabled()) {
+        nu_cell_release(cells);
+        return;
+    }
     nu_spec_drop(k);
-    if (g_nu_spec.size() >= 16) g_nu_spec.erase(g_nu_spec.begin());
+    if (g_nu_spec.size() >= 16) {
+        nu_cell_release(&g_nu_spec.front().cells);
+        g_nu_spec.erase(g_nu_spec.begin());
+    }
     NuSpecEntry e;
     e.key = k;
     std::memcpy(e.hs, hs, sizeof(e.hs));
+    e.cells = *cells;
+    *cells = NuCellTab{};
     g_nu_spec.push_back(e);
+}
+// a search that ran an entry's plan without tables and built them for keeping: they become the entry's
+static void nu_spec_attach(const NuSpecKey& k, NuCellTab* cells) {
+    for (NuSpecEntry& e : g_nu_spec)
+        if (e.key == k && !e.cells.p && !nu_spec_disabled()) {
+            e.cells = *cells;
+            *cells = NuCellTab{};
+            return;
+        }
+    nu_cell_release(cells);
 }
 
 // Row groups of trials [first, first + count): the first row's segment, the full rows between, the last row's
@@ -1927,7 +2078,8 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
                         int64_t nf, int64_t nrows_grid, const double* c2, const double* hs, bool twod, int nharm,
                         int stat, int64_t first,
                         int64_t count, double* out, bool timed, int64_t* nfixed, bool no_fixup, bool* applicable,
-                        double* best, bool* best_done, int* nflag, bool* mismatch) {
+                        double* best, bool* best_done, int* nflag, bool* mismatch, const NuCellTab* cached,
+                        NuCellTab* keep) {
     *applicable = false;
     *best_done = false;
     *nfixed = 0;
@@ -1955,6 +2107,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
         }
     g_last_nufft_gather = gather_grid ? 1 : 0;
     for (double& w : g_nu_work) w = 0.0;
+    g_last_cells_built = g_last_cells_reused = 0;
     // buffers sized for the largest group
     int64_t Bmax = 0, nfmax = 0, csmax = 0, nrow_all = 0;
     for (const NuPlan& pl : plans) {
@@ -1983,13 +2136,23 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
     const int lanes_env = lanes_s ? atoi(lanes_s) : 0;
     ARGCHK(lanes_env == 0 || lanes_env == 1 || lanes_env == 2 || lanes_env == 4 || lanes_env == 8,
            "CRIMP_NUFFT_LANES must be 1, 2, 4 or 8");
-    int64_t starts_max = 0;  // the cell gather's start tables of the largest group
+    int64_t starts_max = 0, starts_all = 0;  // the cell gather's start tables of the largest group, of all groups
+    std::vector<int64_t> starts_off;         // each group's tables within starts_all
     if (gather_grid)
         for (const NuPlan& pl : plans) {
             int64_t tot = 0;
             for (int k = 1; k <= nharm; ++k) tot += pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 2;
             starts_max = std::max<int64_t>(starts_max, tot);
+            starts_off.push_back(starts_all);
+            starts_all += tot;
         }
+    // The start tables: the cached plan's (cells_reuse: no cell-start pass, the gathers check them), or built by this
+    // search -- into memory the plan cache will own (cells_keep: every group's tables side by side) when the search
+    // may be stored and they are under the cap, else into scratch, one group after the other in the same place.
+    const bool cells_reuse = gather_grid && cached && cached->p && cached->len == starts_all;
+    const bool cells_keep = gather_grid && !cells_reuse && keep && starts_all > 0 && !nu_spec_disabled() &&
+                            !nu_cell_disabled() && starts_all * (int64_t)sizeof(int64_t) <= nu_cell_cap_bytes() &&
+                            nu_cell_acquire(keep, starts_all);
     double* U = nullptr;
     double2 *W = nullptr, *Y = nullptr, *CS = nullptr;
     int64_t* ctab = nullptr;
@@ -2001,7 +2164,12 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
         HIPCHK(sc.alloc(&U, (size_t)(ubytes / 8)));
         HIPCHK(sc.alloc(&ctab, (size_t)(2 * kNuPassMax * nchunk)));
     }
-    if (starts_max > 0) HIPCHK(sc.alloc(&cstart, (size_t)starts_max));
+    if (cells_reuse)
+        cstart = cached->p;  // read only
+    else if (cells_keep)
+        cstart = keep->p;
+    else if (starts_max > 0)
+        HIPCHK(sc.alloc(&cstart, (size_t)starts_max));
     HIPCHK(sc.alloc(&W, (size_t)(Bmax * gw)));
     HIPCHK(sc.alloc(&Y, (size_t)Bmax));
     HIPCHK(sc.alloc(&CS, (size_t)csmax));
@@ -2060,7 +2228,9 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
     const double2* cis = nullptr;
     const double2* cis2 = nullptr;
     const double* bc = nullptr;
+    size_t iplan = 0;
     for (const NuPlan& pl : plans) {
+        const size_t ip = iplan++;
         if (pl.lnfft != cur_lnfft) {  // tables for this group's n (a group's first launch follows their upload)
             const int rc = nu_tables(sc, s, pl.lnfft, &T, &cis, &bc, &cis2);
             if (rc) return rc;
@@ -2153,7 +2323,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
         };
         if (gather_grid) {
             std::vector<int64_t> soff((size_t)nharm);
-            int64_t off = 0;
+            int64_t off = cells_reuse || cells_keep ? starts_off[ip] : 0;
             // no zeroing of the start tables: on time-sorted photons every entry is written (each cell's first
             // photon writes it), and on unsorted ones the gathers read none of them (k_nu_gather exits on *bad)
             for (int k0 = 1; k0 <= nharm; k0 += kNuCellK) {
@@ -2167,6 +2337,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
                     soff[(size_t)(k - 1)] = off;
                     off += ca.span[j] + 1;
                 }
+                if (cells_reuse) continue;  // the layout only
                 const unsigned cb = (unsigned)std::min<int64_t>(cdiv(cdiv(n, 2), 256 * kNuCellU), 2048);
                 if ((reinterpret_cast<uintptr_t>(t) & 15u) == 0)
                     k_nu_cellstart<true><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1);
@@ -2174,7 +2345,12 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
                     k_nu_cellstart<false><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1);
                 HIPCHK(hipGetLastError());
             }
-            HIPCHK(span(kNuClsCellStart));
+            if (cells_reuse) {
+                g_last_cells_reused += nharm;
+            } else {
+                g_last_cells_built += nharm;
+                HIPCHK(span(kNuClsCellStart));
+            }
             for (int64_t rb = pl.r0; rb < pl.r1; rb += kNuGatherRows) {
                 const int nrow = (int)std::min<int64_t>(kNuGatherRows, pl.r1 - rb);
                 const int64_t tb0 = std::max<int64_t>(first, rb * nf) - first;
@@ -2217,8 +2393,8 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
                         g_nu_work[kNuClsSpread] += 8.0 * (double)n + 16.0 * (double)P * nrow * (double)gcount;
                     }
                     S.blk0[S.nk] = blocks;
-                    launch_gather(twod, blocks, t, t0, cstart, nfft, pl.s1, pl.fch, pl.fcl, twod ? c2 + rb : nullptr,
-                                  nrow, P, S, nflag + 1, cis2, W, s);
+                    launch_gather(twod, cells_reuse, blocks, t, t0, cstart, nfft, pl.s1, pl.fch, pl.fcl,
+                                  twod ? c2 + rb : nullptr, nrow, P, S, nflag + 1, cis2, W, s);
                     HIPCHK(hipGetLastError());
                     HIPCHK(span(kNuClsSpread));
                     for (int jj = 0; jj < S.nk; ++jj) {
@@ -2318,7 +2494,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, 
     HIPCHK(d2h(s, fl, nflag, (best ? 8 : 2) * sizeof(int)));
     if (fl[1]) {  // photons out of order (found by the cell starts), or a cached plan that no longer holds (2):
         *applicable = false;  // nothing computed, the default path (or a fresh plan) runs
-        *mismatch = fl[1] == 2;
+        *mismatch = (fl[1] & 2) != 0;
         g_last_search_path = 0;
         return CRIMP_OK;
     }

@@ -127,6 +127,10 @@ int crimp_last_nufft_plan(int64_t* fft_length, int32_t* moments, int32_t* gather
  * spread, [2] merge, [3] FFT pass 1, [4] FFT pass 2 (with the moment sum), [5] the removed separate moment sum (always
  * 0, kept for the layout), [6] finalize; returns 7. For bench.py's rooflines, not in the reference. */
 int crimp_last_nufft_work(double* work, int32_t cap);
+/* Cell-start tables (one per row group and harmonic of a cell-gather plan) the last NUFFT search built with
+ * k_nu_cellstart / took from the plan cache (a repeated search over the same buffers: its gathers check them against
+ * the photons). Both 0 for an MFMA-slot plan. Measurement hook for tests and bench.py, not in the reference. */
+int crimp_last_nufft_cells(int64_t* built, int64_t* reused);
 /* Brute-grid norms evaluated per phShift by the last crimp_toa_fit with CRIMP_TOA_BRUTE (the pruned candidates of
  * lmfit's 20-norm lattice, padded to 2, 4 or 20, less the lazy norms the eight-factor grid leaves out; 0 without a
  * brute grid). Measurement hook for bench.py's
