@@ -2217,62 +2217,77 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
         const bool nu_try = nufft && nf >= 64;
         int* nuflags = nullptr;  // the NUFFT's device flags (fix-up count, photon order / plan check, best trial)
         if (nu_try) HIPCHK(sc.alloc(&nuflags, 8));
-        const bool gather_form = nu_gather_form(twod ? nfd : 1);
-        // A repeated search over the same buffers reuses its last plan (nu_spec_find): the progression check and
+        NuSearchIn nu;
+        nu.t = dtm;
+        nu.t0 = t0;
+        nu.freq = dfr;
+        nu.c2 = dc2;
+        nu.twod = twod;
+        nu.shape.n = n;
+        nu.shape.nf = nf;
+        nu.shape.nrows_grid = twod ? nfd : 1;
+        nu.shape.nharm = nharm;
+        nu.shape.stat = stat;
+        nu.shape.first = first;
+        nu.shape.count = count;
+        nu.shape.want_best = best != nullptr;
+        nu.hooks = NuHooks::from_env();
+        nu.hs = nu_hs;
+        nu.out = dout;
+        nu.best = best;
+        nu.timed = flags & CRIMP_FLAG_TIME_KERNELS;
+        nu.no_fixup = (flags & CRIMP_FLAG_NO_FIXUP) != 0;
+        nu.nflag = nuflags;
+        const bool gather_form = nu_gather_form(nu.shape.nrows_grid, nu.hooks);
+        // A repeated search over the same buffers reuses its last plan (NuPlanCache::find): the progression check and
         // the plan's scalars are recomputed on the device and compared there (k_ap_final), every NUFFT kernel that
         // reads photon-derived tables exits if they differ, and the host, reading the result flags anyway at the
         // end, redoes the search from a fresh plan -- one host round trip per search instead of two.
         // A cell-gather plan's start tables are kept with it: the repeated search skips the cell-start pass too, and
         // its gathers check the tables against the photons they read (k_nu_gather, CHECK; the same flag and redo).
-        NuSpecKey key{};
+        const NuSpecKey key = NuPlanCache::key(dtm, dfr, nu.shape, twod ? nfd : 0, t0, gather_form);
+        NuPlanCache::Hold cells(g_nu_cache);
+        nu.keep = &cells.t;
         bool spec_mismatch = false;
-        struct CellHold {  // tables built for keeping: released unless the plan cache takes them
-            NuCellTab t;
-            ~CellHold() { nu_cell_release(&t); }
-        } cells;
-        if (nu_try && !f64) {
-            key = nu_spec_key(dtm, n, t0, dfr, nf, twod ? nfd : 0, nharm, stat, first, count, gather_form);
+        // One attempt: the progression check, the search, then what the plan cache keeps of it. From the cache entry
+        // (from_cache; nothing runs without one) the check compares on the device and reads nothing back; without it
+        // the check reads the plan's scalars back, for the exact rule too.
+        auto nu_attempt = [&](bool from_cache) -> int {
             NuExpect ex{};
             NuCellTab cached;
-            if (nu_spec_find(key, nu_hs, &cached)) {
+            if (from_cache) {
+                if (!g_nu_cache.find(key, nu.hooks, nu_hs, &cached)) return CRIMP_OK;
                 for (int q = 0; q < 4; ++q) ex.v[q] = nu_hs[q];
                 ex.on = 1;
                 ex.check_order = gather_form ? 0 : 1;
-                rc = grid_is_progression(sc, s, dfr, nf, &ap, &progression, dtm, t0, n, nu_hs, !gather_form, nuflags,
-                                         &ex);
-                if (rc) return rc;
-                int64_t nfix = 0;
-                rc = nufft_search(sc, s, dtm, t0, n, dfr, nf, twod ? nfd : 1, dc2, nu_hs, twod, nharm, stat, first,
-                                  count, dout, flags & CRIMP_FLAG_TIME_KERNELS, &nfix,
-                                  (flags & CRIMP_FLAG_NO_FIXUP) != 0, &done, best, &best_done, nuflags, &spec_mismatch,
-                                  &cached, &cells.t);
-                if (rc) return rc;
-                if (done) g_last_fixups = nfix;
-                if (done && cells.t.p) nu_spec_attach(key, &cells.t);  // (an entry stored without tables)
-                nu_cell_release(&cells.t);
-                if (spec_mismatch) nu_spec_drop(key);
-                // not done and no mismatch: photons out of order under a still-valid progression (the exact rule)
             }
-        }
-        if (!done && (!progression || spec_mismatch) && !f64 && (exact_grid || nu_try)) {
             progression = false;
-            rc = grid_is_progression(sc, s, dfr, nf, &ap, &progression, nufft ? dtm : nullptr, t0, n, nu_hs,
-                                     !gather_form, nuflags, nullptr);
-            if (rc) return rc;
-            if (progression && nu_try) {  // NUFFT; unsorted photons or no plan fall through to the exact rule
-                int64_t nfix = 0;
-                bool mm = false;
-                rc = nufft_search(sc, s, dtm, t0, n, dfr, nf, twod ? nfd : 1, dc2, nu_hs, twod, nharm, stat, first,
-                                  count, dout, flags & CRIMP_FLAG_TIME_KERNELS, &nfix,
-                                  (flags & CRIMP_FLAG_NO_FIXUP) != 0, &done, best, &best_done, nuflags, &mm, nullptr,
-                                  &cells.t);
-                if (rc) return rc;
-                if (done) {  // ended clean (the order flag read back as 0): the plan and its tables are kept
-                    g_last_fixups = nfix;
-                    nu_spec_store(key, nu_hs, &cells.t);
-                }
+            int r = grid_is_progression(sc, s, dfr, nf, &ap, &progression, nufft ? dtm : nullptr, t0, n, nu_hs,
+                                        !gather_form, nuflags, from_cache ? &ex : nullptr);
+            if (r) return r;
+            if (!progression || !nu_try) return CRIMP_OK;  // the exact rule
+            nu.cached = from_cache ? &cached : nullptr;
+            NuSearchOut res;
+            r = nufft_search(sc, s, nu, &res);
+            if (r) return r;
+            done = res.applicable;  // else: unsorted photons, no plan, or a cached plan that no longer holds
+            best_done = res.best_done;
+            if (done) g_last_fixups = res.nfixed;
+            if (!from_cache) {  // ended clean (the order flag read back as 0): the plan and its tables are kept
+                if (done) g_nu_cache.store(key, nu.hooks, nu_hs, &cells.t);
+                return CRIMP_OK;
             }
-        }
+            if (done && cells.t.p) g_nu_cache.attach(key, nu.hooks, &cells.t);  // (an entry stored without tables)
+            g_nu_cache.release(&cells.t);
+            spec_mismatch = res.mismatch;
+            if (spec_mismatch) g_nu_cache.drop(key);
+            // not done and no mismatch: photons out of order under a still-valid progression (the exact rule)
+            return CRIMP_OK;
+        };
+        if (nu_try) rc = nu_attempt(true);
+        if (rc) return rc;
+        if (!done && (!progression || spec_mismatch) && !f64 && (exact_grid || nu_try)) rc = nu_attempt(false);
+        if (rc) return rc;
         const bool factorised = !done && progression && exact_grid;
         if ((flags & CRIMP_FLAG_FORCE_MFMA) && !done && !factorised)
             return set_err(CRIMP_ERR_ARG, "factorised search not applicable (grid is not an arithmetic progression)");

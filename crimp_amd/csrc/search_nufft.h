@@ -33,35 +33,26 @@
 //                 the moments' Bessel-weighted sum at every trial -> (C_k, S_k) kept in registers across the moments.
 //   k_nu_finalize Z^2 / H in the reference's formula order and the certificate (fix-up list, as the exact path); the
 //                 last harmonic's k_nu_rows_iw / k_nu_rows_combine8 launch does it in its epilogue instead.
+//
+// Host: every decision that needs no device pointer -- n and P per row group, the spread form, the buffer sizes, the
+// start-table layout, the gather sets and MFMA passes, the work and launch counts -- is plan_nufft_search
+// (search_nufft_plan.h, no HIP, checked on the CPU by tests/test_nufft_plan.py). nufft_search walks that plan: NuRun
+// holds the stream, the scratch buffers and the timed-span recorder and queues the cell starts, one gather set, one
+// MFMA pass + merge, one FFT + moment sum and one finalize; the flags' single read-back, the out-of-order / mismatch
+// handling and the fix-up follow. NuPlanCache keeps the plans (and start tables) of repeated searches.
 #pragma once
+
+#include "search_nufft_plan.h"  // the constants and kernel-argument structs the host plan fills (NuPass, NuCellArgs,
+                                 // NuGatherSet), the plan itself (plan_nufft_search)
 
 typedef double nu_f64x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kNuCW = 1024;        // photons per wave chunk (256 K-groups of 4 photons)
-constexpr int kNuWaves = 4;        // chunks per 256-thread block
-constexpr int kNuRows = 8;         // trial-grid rows per pass (8 rows x re/im = the 16 MFMA columns)
-constexpr int kNuMaxP = 16;        // moments of the MFMA spread (its 16 A rows)
-constexpr int kNuGatherMaxP = 24;  // moments of the cell-gather spread (registers)
-constexpr int kNuMergeG = 16;      // wrapped cells per merge block
-constexpr int kNuMaxWrap = 32;     // unwrapped cells per wrapped cell (span of the photons over n)
 constexpr int kNuTile = 4096;      // complex elements per FFT block (64 KB of LDS), 16 per thread
-constexpr double kNuEps = 5e-14;   // truncation bound per photon at the grid's edge (below the rounding term kNuRho)
-// Z^2_m with m >= 2: 5e-13. The certificate flags a trial when its power's bound exceeds 1e-6 of the power, and Z^2_m's
-// bound over its power is sum_k (2 |A_k| E + E^2) / sum_k |A_k|^2 -- at E = N (5e-13 + kNuRho) only trials whose every
-// |A_k| is below ~2e-5 N are flagged (none at config 3, P 15 -> 14). Z^2_1 and H keep kNuEps: H = max_m (Z^2_m - 4m + 4)
-// cancels to near 0 on noise, where a larger E flags many more trials for the fp64 fix-up (config 4: 55 at kNuEps).
-constexpr double kNuEpsZm = 5e-13;
 // Rounding bound per photon for the certificate, in units of |A_k|'s scale N: c_i (cis table + fp64 polynomial,
 // angle-addition over <= 8 harmonics: ~20 ulp), the MFMA's fp64 accumulation over <= 256 K-groups per cell run
 // (<= 256 ulp of the run's sum of |terms|, each <= 1), the merge, the FFT (~3 log2 n ulp) and Horner (e^x ulp):
 // < 4e-14 N; kept at 1e-13 N.
 constexpr double kNuRho = 1e-13;
-
-constexpr int kNuPassMax = 10;  // harmonics per MFMA spread pass (k_nu_spread<G>, G <= 10)
-struct NuPass {          // one spread pass: the slot array of each harmonic k0 + kk
-    int64_t gmin[kNuPassMax];   // unwrapped cell of dt[0]
-    int64_t ubase[kNuPassMax];  // offset (doubles) of the harmonic's slots in U
-};
 
 struct NuTw {            // w_n^t = hi[t >> lbits] * lo[t & (2^lbits - 1)], t in [0, n)
     const double2* lo;
@@ -374,10 +365,6 @@ __global__ __launch_bounds__(256) void k_nu_spread(const double* __restrict__ tt
 // unwrapped cells G in [gmin, gmax + 1]; photons are time-sorted, so cell G holds photons [start[G], start[G+1]).
 // Up to kNuCellK harmonics k0 .. k0+nk-1 per launch (one read of the photon times): harmonic k0 + j writes its
 // table at start + off[j] for cells gmin[j] .. gmin[j] + span[j] - 1.
-constexpr int kNuCellK = 4;
-struct NuCellArgs {
-    int64_t gmin[kNuCellK], span[kNuCellK], off[kNuCellK];
-};
 // The cell gather's plans take the photon order from here too (no k_nu_sorted pass): a pair out of order sets *bad
 // (the search then takes the default path) and the writes stay inside the tables (every cell is clamped to its
 // harmonic's range). The tables are not zeroed: on unsorted photons the gathers read none of them (*bad).
@@ -474,16 +461,7 @@ __device__ __forceinline__ double nu_quad_perm(double x) {
     const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xF, 0xF, true);
     return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
-constexpr int kNuGatherRows = 2;
-constexpr int kNuGatherSet = 8;
-struct NuGatherSet {
-    int nk;
-    int k[kNuGatherSet], lanes_log2[kNuGatherSet];
-    int64_t blk0[kNuGatherSet + 1];                       // first block of each harmonic, then the total
-    int64_t gmin[kNuGatherSet], gmax[kNuGatherSet], gbase[kNuGatherSet], gcount[kNuGatherSet];
-    int64_t soff[kNuGatherSet], woff[kNuGatherSet];       // the harmonic's start table and W planes
-};
-// CHECK: the start tables are a cached plan's (nu_spec_find), built from the photons an earlier search read. Every
+// CHECK: the start tables are a cached plan's (NuPlanCache::find), built from the photons an earlier search read. Every
 // lane then verifies what the tables assume of the photons it weights: each sits in the lane's cell G -- the cell
 // k_nu_cellstart forms, (int)rint(k (dt s1)), a product alone, so nothing contracts -- and the photons of a cell do not
 // descend in index order (neighbours through a rotation inside the L-group, checked by the set's first harmonic only:
@@ -1585,38 +1563,20 @@ static int g_last_search_path = 0;  // crimp_last_search_path(): 0 fp64 direct, 
 static int64_t g_last_nufft_n = 0;   // crimp_last_nufft_plan(): the last NUFFT's largest FFT length, its moments,
 static int g_last_nufft_p = 0;       // and its spread form (1 cell gather, 0 MFMA slots)
 static int g_last_nufft_gather = 0;
-// Kernel classes of a NUFFT search (timed spans and work counts): cell starts, spread (cell gather or MFMA slots),
-// merge, FFT pass 1 (columns), FFT pass 2 (rows, with the moment sum), the separate moment sum (its kernel is removed:
-// the slot stays in the reporting ABI and holds 0), finalize.
-enum { kNuClsCellStart, kNuClsSpread, kNuClsMerge, kNuClsPass1, kNuClsPass2, kNuClsCombine, kNuClsFinalize, kNuCls };
-// crimp_last_nufft_work(): the last NUFFT's algorithmic work -- [0] spread fp64 flops, then HBM bytes per class 1..6
-// ([1] the spread's bytes; class 0, the cell starts, is not counted)
+// crimp_last_nufft_work(): the last NUFFT's algorithmic work (NuSearchPlan::work)
 static double g_nu_work[kNuCls] = {0, 0, 0, 0, 0, 0, 0};
+// crimp_last_nufft_cells(): start tables (one per row group and harmonic) the last NUFFT search built / reused
+static int64_t g_last_cells_built = 0, g_last_cells_reused = 0;
 
-// truncation bound of P Chebyshev moments per unit photon weight at x = pi |jc| / n: 2.4 (x/2)^P / P! (nu_bes);
-// invfact = 2.4 / (2^P P!), so that k_nu_finalize's x^P invfact is the bound
-static double nu_trunc(double x, int P, double* invfact) {
-    double f = 1.0, xp = 1.0;
-    for (int p = 1; p <= P; ++p) {
-        f *= 2.0 * (double)p;
-        xp *= x;
-    }
-    *invfact = 2.4 / f;
-    return 2.4 * xp / f;
-}
-
-static int ilog2(int64_t v) {
-    int l = 0;
-    while ((int64_t(1) << l) < v) ++l;
-    return l;
-}
-
-// per-call twiddle (w_n^t) and cis tables, fp64 from long double
-// Twiddle (w_n, two-level) and cis tables for n = 2^lnfft, built once per device and n (long double on the host) and
-// kept for the process: a search reuses them without an upload.
-static int nu_tables(Scratch& sc, hipStream_t s, int lnfft, NuTw* T, const double2** cis, const double** bc,
-                     const double2** cis2) {
-    (void)sc;
+// Twiddle (w_n, two-level), cis and Bessel-series tables for n = 2^lnfft, built once per device and n (long double on
+// the host) and kept for the process: a search reuses them without an upload.
+struct NuTables {
+    NuTw T{};
+    const double2* cis = nullptr;   // 1024 points per turn (k_nu_spread)
+    const double2* cis2 = nullptr;  // 2048 points per turn (k_nu_gather)
+    const double* bc = nullptr;     // nu_bes_series coefficients
+};
+static int nu_tables(hipStream_t s, int lnfft, NuTables* out) {
     static std::mutex mu;
     static std::map<std::pair<int, int>, double2*> cache;
     const int lbits = std::min(lnfft, 11);
@@ -1664,30 +1624,14 @@ static int nu_tables(Scratch& sc, hipStream_t s, int lnfft, NuTw* T, const doubl
             cache[{dev, lnfft}] = d;
         }
     }
-    T->lo = d;
-    T->hi = d + nlo;
-    T->lbits = lbits;
-    T->mask = (int64_t(1) << lnfft) - 1;
-    *cis = d + nlo + nhi;
-    *bc = reinterpret_cast<const double*>(d + nlo + nhi + 1024);
-    *cis2 = d + nlo + nhi + 1024 + kNuBesP * kNuBesM / 2;
+    out->T.lo = d;
+    out->T.hi = d + nlo;
+    out->T.lbits = lbits;
+    out->T.mask = (int64_t(1) << lnfft) - 1;
+    out->cis = d + nlo + nhi;
+    out->bc = reinterpret_cast<const double*>(d + nlo + nhi + 1024);
+    out->cis2 = d + nlo + nhi + 1024 + kNuBesP * kNuBesM / 2;
     return CRIMP_OK;
-}
-
-// The FFT input's occupied rows a in [alo, alo + acnt) (mod n1) of the four-step view [n1][n2]: the wrapped cells
-// of harmonic k's unwrapped range [gmin, gmax], widened to whole rows; a single-pass FFT (n1 = 1) or a range that
-// wraps the grid takes all rows. Only those rows are spread into and read by pass 1; the others are zero.
-static void nu_occupied(int64_t gmin, int64_t gmax, int lnfft, int ln1, int* alo, int* acnt) {
-    const int64_t nfft = int64_t(1) << lnfft, n1 = int64_t(1) << ln1;
-    const int ln2 = lnfft - ln1;
-    *alo = 0;
-    *acnt = (int)n1;
-    if (ln1 == 0 || gmax - gmin + 1 >= nfft) return;
-    const int64_t glo = gmin & (nfft - 1), ghi = glo + (gmax - gmin);  // unwrapped end
-    const int64_t a0 = glo >> ln2, a1 = ghi >> ln2;
-    if (a1 - a0 + 1 >= n1) return;
-    *alo = (int)a0;
-    *acnt = (int)(a1 - a0 + 1);
 }
 
 template <bool TWOD>
@@ -1702,7 +1646,6 @@ static void nu_launch_spread(int G, dim3 grid, hipStream_t s, const double* tt, 
 #undef CRIMP_NS
 }
 
-// Budget of the NUFFT path's device buffers (CRIMP_NUFFT_BUDGET_MB, default 6144): slots, FFT ping-pong, sums.
 template <int R, bool TWOD, bool CHECK>
 static void launch_gather_r(int64_t blocks, const double* tt, double t0, const int64_t* start, int64_t nfft, double s1,
                             double fch, double fcl, const double* c2, int nrow, int P, const NuGatherSet& S,
@@ -1748,315 +1691,6 @@ static int64_t nu_cus() {  // compute units of the current device (persistent gr
     return ncu;
 }
 
-// CRIMP_NUFFT_FINAL=separate: the k_nu_finalize launch after every row batch instead of the fused finalize (A/B and
-// identity test hook, read per call)
-static bool nu_final_separate() {
-    const char* e = getenv("CRIMP_NUFFT_FINAL");
-    return e && !strcmp(e, "separate");
-}
-
-static int64_t nufft_budget() {
-    static int64_t b = -1;
-    if (b < 0) {
-        const char* e = getenv("CRIMP_NUFFT_BUDGET_MB");
-        const long long mb = e ? atoll(e) : 6144;
-        b = (int64_t)(mb > 0 ? mb : 6144) << 20;
-    }
-    return b;
-}
-
-// One group of rows that share their trial segment: rows [r0, r1), trials j0 .. j0+nseg-1 of each, planned on that
-// segment alone (a rank's slice of a row is its own progression, so a sharded search costs its share).
-struct NuPlan {
-    int64_t r0 = 0, r1 = 0, j0 = 0, nseg = 0, h = 0;  // jc = j - (j0 + h) in [-h, nseg - 1 - h]
-    int lnfft = 0, P = 0;
-    double invfact = 1.0, s1 = 0.0, fch = 0.0, fcl = 0.0;
-    std::vector<int64_t> gmin, gmax;                     // unwrapped cells of dt[0], dt[n-1] per harmonic
-};
-
-// n and P: among the powers of two n >= nseg (up to 2^24) whose edge truncation (nu_trunc) <= kNuEps within P <= pmax
-// moments, the one with the least FFT work n P; false when none exists or the photons wrap the grid more than
-// kNuMaxWrap times
-static bool nu_plan(NuPlan* pl, double delta, double f0, double dt0, double dtn, int nharm, int pmax, double eps) {
-    // an ascending progression only: with delta < 0 the cells of the later photons come first (s1 < 0) and every
-    // table below would be sized negative (a descending grid takes the exact rule)
-    if (!(delta > 0.0) || !std::isfinite(delta) || !std::isfinite(f0)) return false;
-    const int64_t h = pl->nseg / 2;
-    pl->h = h;
-    int lnfft = 0, P = 0;
-    double invfact = 1.0;
-    for (int l = std::max(ilog2(pl->nseg), 6); l <= 24; ++l) {
-        const double x = M_PI * (double)std::max<int64_t>(h, pl->nseg - 1 - h) / (double)(int64_t(1) << l);
-        int p = 1;
-        while (p <= pmax && nu_trunc(x, p, &invfact) > eps) ++p;
-        if (p > pmax) continue;
-        if (lnfft == 0 || ((int64_t)p << l) < ((int64_t)P << lnfft)) {
-            lnfft = l;
-            P = p;
-        }
-        if (p <= 4) break;  // larger n only adds work
-    }
-    if (lnfft == 0) return false;
-    nu_trunc(0.0, P, &invfact);
-    pl->lnfft = lnfft;
-    pl->P = P;
-    pl->invfact = invfact;
-    const int64_t nfft = int64_t(1) << lnfft;
-    pl->s1 = (double)nfft * delta;
-    // fc = f_0 + (j0 + h) delta in double-double (the whole grid's progression model, whatever the segment)
-    const double c = (double)(pl->j0 + h);
-    const double hp = c * delta, hpe = std::fma(c, delta, -hp);
-    const double fch = f0 + hp, bb = fch - f0;  // TwoSum(f0, hp)
-    pl->fch = fch;
-    pl->fcl = ((f0 - (fch - bb)) + (hp - bb)) + hpe;
-    // the kernel's arithmetic: rint(k * (dt * s1))
-    const double u0 = dt0 * pl->s1, un = dtn * pl->s1;
-    // The kernels convert cells with 32-bit rint (k_nu_spread, k_nu_cellstart, k_nu_gather): every cell of every
-    // harmonic, one FFT length of margin included, must fit an int -- a t0 far from the photons (t0 = 0 with MJD
-    // seconds) can push |G| past 2^31 although the span is small. The plan is declined then (the exact rule runs).
-    const double glim = 2147483647.0 - (double)nfft;
-    pl->gmin.assign((size_t)nharm, 0);
-    pl->gmax.assign((size_t)nharm, 0);
-    for (int k = 1; k <= nharm; ++k) {
-        const double a = (double)k * u0, b = (double)k * un;
-        if (!(std::fabs(a) < glim && std::fabs(b) < glim)) return false;  // NaN declines too
-        pl->gmin[(size_t)(k - 1)] = (int64_t)std::rint(a);
-        pl->gmax[(size_t)(k - 1)] = (int64_t)std::rint(b);
-        // descending cells (a descending grid, delta < 0, or photons out of order at the ends) would size the
-        // slot and start tables negative: declined
-        if (pl->gmax[(size_t)(k - 1)] < pl->gmin[(size_t)(k - 1)]) return false;
-        if ((pl->gmax[(size_t)(k - 1)] - pl->gmin[(size_t)(k - 1)]) / nfft + 1 > kNuMaxWrap) return false;
-    }
-    return true;
-}
-
-// Z^2 / H by NUFFT over trials [first, first + count) of the fd-outer grid (nf trials per row, arithmetic
-// progression with step ap[0]). *applicable = false (nothing computed) for unsorted photons or an out-of-range plan:
-// the caller takes the exact path.
-// The spread form of a grid of nrows_grid rows: the cell gather for <= kNuGatherRows rows, the MFMA slots otherwise
-// (CRIMP_NUFFT_SPREAD=gather|mfma forces one, a test hook). Decided from the whole grid, so that row shards compute
-// exactly what the whole grid does.
-static bool nu_gather_form(int64_t nrows_grid) {
-    const char* spread_env = getenv("CRIMP_NUFFT_SPREAD");
-    return spread_env && !strcmp(spread_env, "gather")  ? true
-           : spread_env && !strcmp(spread_env, "mfma") ? false
-                                                       : nrows_grid <= kNuGatherRows;
-}
-
-// hs: [delta, f0, dt[0], dt[n-1], unsorted flag (int bits)] as grid_is_progression read them back (the flag only for
-// MFMA-slot plans: a cell-gather plan checks the order in its cell-start pass).
-// t: photon times (seconds), t0 the search's reference time: the kernels form dt = t - t0 as k_search_prep does;
-// dt (and dt^2) arrays are made only for a fix-up.
-// A search's last plan, keyed by its buffers and shape (crimp_search reuses it on the next identical call; the device
-// re-checks its scalars, k_ap_final). Up to 16 entries, the oldest dropped first.
-struct NuSpecKey {
-    const void* t;
-    const void* f;
-    int64_t n, nf, nfd, first, count;
-    double t0;
-    int nharm, stat, dev, gather;
-    bool operator==(const NuSpecKey& o) const {
-        return t == o.t && f == o.f && n == o.n && nf == o.nf && nfd == o.nfd && first == o.first &&
-               count == o.count && t0 == o.t0 && nharm == o.nharm && stat == o.stat && dev == o.dev &&
-               gather == o.gather;
-    }
-};
-// A cell-gather plan's start tables (k_nu_cellstart), every row group's and harmonic's as nufft_search lays them out,
-// in device memory of the cache's own: built once by a search that ended clean, never written again (every index in
-// them lies in [0, n] whatever the photon buffer holds later) and read by the later searches that find the entry,
-// whose gathers check them against the photons (k_nu_gather, CHECK). Every search returns with its stream drained and
-// calls are serialised (g_mutex), so a table is complete before any later call, on whatever stream, reads it: no
-// event is needed. Memory: at most one allocation per entry (16) plus one spare -- a dropped or evicted entry's
-// allocation becomes the spare, or is freed when there is one already, and a new table takes the spare when it fits.
-// A search that reuses its table allocates and frees nothing.
-struct NuCellTab {
-    int64_t* p = nullptr;
-    int64_t cap = 0, len = 0;  // int64 entries allocated / used (the sum of every group's tables)
-    int dev = 0;               // the device it was allocated on
-};
-static NuCellTab g_nu_cell_spare;
-// tables above this many bytes are rebuilt by every search: 1/32 of the NUFFT's budget, 64 MB at most
-static int64_t nu_cell_cap_bytes() { return std::min<int64_t>(nufft_budget() / 32, int64_t(64) << 20); }
-static bool nu_cell_disabled() {  // CRIMP_NUFFT_CELL_CACHE=0: the plan is reused, its tables are rebuilt (A/B hook)
-    const char* e = getenv("CRIMP_NUFFT_CELL_CACHE");
-    return e && !strcmp(e, "0");
-}
-static void nu_cell_release(NuCellTab* t) {
-    if (t->p) {
-        if (!g_nu_cell_spare.p) {
-            g_nu_cell_spare = *t;
-        } else {
-            (void)hipFree(t->p);
-        }
-    }
-    *t = NuCellTab{};
-}
-// room for len entries (the spare when it fits and is not more than twice too large); false: no memory, no caching
-static bool nu_cell_acquire(NuCellTab* t, int64_t len) {
-    NuCellTab& sp = g_nu_cell_spare;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (sp.p && (sp.dev != dev || sp.cap < len || sp.cap > 2 * len + (int64_t(1) << 17))) {
-        (void)hipFree(sp.p);
-        sp = NuCellTab{};
-    }
-    if (sp.p) {
-        *t = sp;
-        sp = NuCellTab{};
-    } else {
-        void* p = nullptr;
-        if (hipMalloc(&p, (size_t)len * sizeof(int64_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        t->p = static_cast<int64_t*>(p);
-        t->cap = len;
-        t->dev = dev;
-    }
-    t->len = len;
-    return true;
-}
-// crimp_last_nufft_cells(): start tables (one per row group and harmonic) the last NUFFT search built / reused
-static int64_t g_last_cells_built = 0, g_last_cells_reused = 0;
-struct NuSpecEntry {
-    NuSpecKey key;
-    double hs[5];
-    NuCellTab cells;  // none (p == nullptr): an MFMA-slot plan, tables above the cap, or CRIMP_NUFFT_CELL_CACHE=0
-};
-static std::vector<NuSpecEntry> g_nu_spec;
-static bool nu_spec_disabled() {  // CRIMP_NUFFT_PLAN_CACHE=0: every search reads its plan back (A/B hook)
-    const char* e = getenv("CRIMP_NUFFT_PLAN_CACHE");
-    return e && !strcmp(e, "0");
-}
-static NuSpecKey nu_spec_key(const double* t, int64_t n, double t0, const double* f, int64_t nf, int64_t nfd,
-                             int nharm, int stat, int64_t first, int64_t count, bool gather) {
-    NuSpecKey k{};
-    k.stat = stat;
-    k.t = t;
-    k.f = f;
-    k.n = n;
-    k.nf = nf;
-    k.nfd = nfd;
-    k.first = first;
-    k.count = count;
-    k.t0 = t0;
-    k.nharm = nharm;
-    k.gather = gather ? 1 : 0;
-    (void)hipGetDevice(&k.dev);
-    return k;
-}
-// *cells: the entry's start tables (still the entry's own), none where it has none or the cell cache is off
-static bool nu_spec_find(const NuSpecKey& k, double* hs, NuCellTab* cells) {
-    *cells = NuCellTab{};
-    if (nu_spec_disabled()) return false;
-    for (const NuSpecEntry& e : g_nu_spec)
-        if (e.key == k) {
-            std::memcpy(hs, e.hs, sizeof(e.hs));
-            if (!nu_cell_disabled()) *cells = e.cells;
-            return true;
-        }
-    return false;
-}
-static void nu_spec_drop(const NuSpecKey& k) {
-    for (size_t i = 0; i < g_nu_spec.size(); ++i)
-        if (g_nu_spec[i].key == k) {
-            nu_cell_release(&g_nu_spec[i].cells);
-            g_nu_spec.erase(g_nu_spec.begin() + (std::ptrdiff_t)i);
-            return;
-        }
-}
-// cells: the tables the search built for keeping (nu_cell_acquire), now the entry's; released where nothing is stored
-static void nu_spec_store(const NuSpecKey& k, const double* hs, NuCellTab* cells) {
-    if (nu_spec_disabled()) {
-        nu_cell_release(cells);
-        return;
-    }
-    nu_spec_drop(k);
-    if (g_nu_spec.size() >= 16) {
-        nu_cell_release(&g_nu_spec.front().cells);
-        g_nu_spec.erase(g_nu_spec.begin());
-    }
-    NuSpecEntry e;
-    e.key = k;
-    std::memcpy(e.hs, hs, sizeof(e.hs));
-    e.cells = *cells;
-    *cells = NuCellTab{};
-    g_nu_spec.push_back(e);
-}
-// a search that ran an entry's plan without tables and built them for keeping: they become the entry's
-static void nu_spec_attach(const NuSpecKey& k, NuCellTab* cells) {
-    for (NuSpecEntry& e : g_nu_spec)
-        if (e.key == k && !e.cells.p && !nu_spec_disabled()) {
-            e.cells = *cells;
-            *cells = NuCellTab{};
-            return;
-        }
-    nu_cell_release(cells);
-}
-
-// Row groups of trials [first, first + count): the first row's segment, the full rows between, the last row's
-// segment, each planned (nu_plan for nharm + 1 harmonics: an MFMA spread pass may run one past nharm). False when a
-// segment is shorter than 64 trials or has no plan.
-static bool nu_row_groups(std::vector<NuPlan>* plans, int64_t first, int64_t count, int64_t nf, double delta, double f0,
-                          double dt0, double dtn, int nharm, int pmax, double eps) {
-    const int64_t r_lo = first / nf, r_hi = (first + count - 1) / nf;
-    for (int64_t r = r_lo; r <= r_hi;) {
-        const int64_t a = std::max<int64_t>(first, r * nf) - r * nf, b = std::min<int64_t>(first + count, (r + 1) * nf) - r * nf;
-        int64_t r1 = r + 1;
-        if (a == 0 && b == nf)
-            while (r1 <= r_hi && std::min<int64_t>(first + count, (r1 + 1) * nf) - r1 * nf == nf) ++r1;
-        NuPlan pl;
-        pl.r0 = r;
-        pl.r1 = r1;
-        pl.j0 = a;
-        pl.nseg = b - a;
-        if (pl.nseg < 64 || !nu_plan(&pl, delta, f0, dt0, dtn, nharm + 1, pmax, eps)) return false;
-        plans->push_back(std::move(pl));
-        r = r1;
-    }
-    return true;
-}
-
-// The MFMA spread's passes, (k0, harmonics) each, and the bytes of their largest slot array. Harmonics per pass: the
-// largest size in {10, 8, 6, 4, 2} (<= Gmax) the remaining harmonics fill, allowing one past nharm (its cells are
-// planned, nu_row_groups): H_20 runs as 10 + 10 (two photon passes; 8 + 8 + 4 paid the per-photon phase and cis three
-// times). Gmax: the largest of 10, 8, 4, 2 whose slots fit the budget beside the fixed_bytes of W, Y and the sums.
-static int64_t nu_spread_passes(std::vector<std::pair<int, int>>* passes, const std::vector<NuPlan>& plans, int nharm,
-                                int64_t nchunk, int64_t fixed_bytes) {
-    int64_t ubytes = 0;
-    for (int Gmax = 10;; Gmax = Gmax == 10 ? 8 : Gmax / 2) {  // Gmax >= 2
-        passes->clear();
-        ubytes = 0;
-        for (int k0 = 1; k0 <= nharm;) {
-            const int rem = nharm - k0 + 1;
-            int gl = 2;
-            for (int cand : {10, 8, 6, 4, 2})
-                if (cand <= Gmax && cand <= rem + 1) {
-                    gl = cand;
-                    break;
-                }
-            for (const NuPlan& pl : plans) {
-                const int64_t SLmax = 2 * (int64_t)pl.P * std::min<int64_t>(kNuRows, pl.r1 - pl.r0);
-                int64_t sl = 0;
-                for (int k = k0; k < k0 + gl; ++k)
-                    sl += (pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 1 + nchunk) * SLmax;
-                ubytes = std::max<int64_t>(ubytes, sl * 8);
-            }
-            passes->emplace_back(k0, gl);
-            k0 += gl;
-        }
-        if (Gmax == 2 || ubytes + fixed_bytes <= nufft_budget()) break;
-    }
-    return ubytes;
-}
-
-// CRIMP_NUFFT_ROWS4096=0: every FFT by the generic kernels (k_nu_fft_cols, k_nu_fft_rows_combine, k_nu_finalize) -- the
-// reference the specialised column and row kernels are tested against, read per call
-static bool nu_generic_fft() {
-    const char* e = getenv("CRIMP_NUFFT_ROWS4096");
-    return e && !strcmp(e, "0");
-}
-
 // The radix-8 row kernels' dynamic LDS (above the 64 KB default), set once per device
 static int nu_rows_lds_attrs() {
     static std::mutex mu;
@@ -2074,441 +1708,496 @@ static int nu_rows_lds_attrs() {
     return CRIMP_OK;
 }
 
-static int nufft_search(Scratch& sc, hipStream_t s, const double* t, double t0, int64_t n, const double* freq,
-                        int64_t nf, int64_t nrows_grid, const double* c2, const double* hs, bool twod, int nharm,
-                        int stat, int64_t first,
-                        int64_t count, double* out, bool timed, int64_t* nfixed, bool no_fixup, bool* applicable,
-                        double* best, bool* best_done, int* nflag, bool* mismatch, const NuCellTab* cached,
-                        NuCellTab* keep) {
-    *applicable = false;
-    *best_done = false;
-    *nfixed = 0;
-    *mismatch = false;
-    int bad = 0;
-    memcpy(&bad, hs + 4, sizeof(int));
-    if (bad) return CRIMP_OK;
-    const double delta = hs[0], f0 = hs[1], dt0 = hs[2], dtn = hs[3];
-    const int64_t nchunk = cdiv(n, kNuCW);
-    // spread form: the cell gather (VALU, one lane per wrapped cell) for grids of <= kNuGatherRows rows, the MFMA
-    // slots otherwise -- decided from the whole grid, so that row shards compute exactly what the whole grid does
-    // (CRIMP_NUFFT_SPREAD=gather|mfma forces one, a test hook)
-    const bool gather_grid = nu_gather_form(nrows_grid);
-    std::vector<NuPlan> plans;
-    if (!nu_row_groups(&plans, first, count, nf, delta, f0, dt0, dtn, nharm, gather_grid ? kNuGatherMaxP : kNuMaxP,
-                       stat == 0 && nharm >= 2 ? kNuEpsZm : kNuEps))
-        return CRIMP_OK;
-    *applicable = true;
-    g_last_search_path = 2;
-    g_last_nufft_n = 0;
-    for (const NuPlan& pl : plans)
-        if ((int64_t(1) << pl.lnfft) > g_last_nufft_n) {
-            g_last_nufft_n = int64_t(1) << pl.lnfft;
-            g_last_nufft_p = pl.P;
+// ---- the plan cache ----
+// A search's last plan, keyed by its buffers and shape (crimp_search reuses it on the next identical call; the device
+// re-checks its scalars, k_ap_final).
+struct NuSpecKey {
+    const void* t;
+    const void* f;
+    int64_t n, nf, nfd, first, count;
+    double t0;
+    int nharm, stat, dev, gather;
+    bool operator==(const NuSpecKey& o) const {
+        return t == o.t && f == o.f && n == o.n && nf == o.nf && nfd == o.nfd && first == o.first &&
+               count == o.count && t0 == o.t0 && nharm == o.nharm && stat == o.stat && dev == o.dev &&
+               gather == o.gather;
+    }
+};
+// A cell-gather plan's start tables (k_nu_cellstart), every row group's and harmonic's as plan_nufft_search lays them
+// out, in device memory of the cache's own
+struct NuCellTab {
+    int64_t* p = nullptr;
+    int64_t cap = 0, len = 0;  // int64 entries allocated / used (the sum of every group's tables)
+    int dev = 0;               // the device it was allocated on
+};
+// Up to 16 plans, the oldest dropped first, each with its read-back scalars hs and, for a cell-gather plan under the
+// cap (NuHooks::cell_cap), its start tables: built once by a search that ended clean, never written again (every index
+// in them lies in [0, n] whatever the photon buffer holds later) and read by the later searches that find the entry,
+// whose gathers check them against the photons (k_nu_gather, CHECK). Every search returns with its stream drained and
+// calls are serialised (g_mutex), so a table is complete before any later call, on whatever stream, reads it: no
+// event is needed. Memory: at most one allocation per entry (16) plus one spare -- a dropped or evicted entry's
+// allocation becomes the spare, or is freed when there is one already, and a new table takes the spare when it fits.
+// A search that reuses its table allocates and frees nothing.
+class NuPlanCache {
+  public:
+    struct Hold {  // a table a search built for keeping: released unless an entry takes it (store, attach)
+        NuPlanCache& c;
+        NuCellTab t;
+        explicit Hold(NuPlanCache& cache) : c(cache) {}
+        ~Hold() { c.release(&t); }
+    };
+    static NuSpecKey key(const double* t, const double* f, const NuSearchShape& sh, int64_t nfd, double t0, bool gather) {
+        NuSpecKey k{};
+        k.t = t;
+        k.f = f;
+        k.n = sh.n;
+        k.nf = sh.nf;
+        k.nfd = nfd;
+        k.first = sh.first;
+        k.count = sh.count;
+        k.t0 = t0;
+        k.nharm = sh.nharm;
+        k.stat = sh.stat;
+        k.gather = gather ? 1 : 0;
+        (void)hipGetDevice(&k.dev);
+        return k;
+    }
+    // *cells: the entry's start tables (still the entry's own), none where it has none or the cell cache is off
+    bool find(const NuSpecKey& k, const NuHooks& hooks, double* hs, NuCellTab* cells) const {
+        *cells = NuCellTab{};
+        if (hooks.plan_cache_off) return false;
+        for (const Entry& e : entries_)
+            if (e.key == k) {
+                std::memcpy(hs, e.hs, sizeof(e.hs));
+                if (!hooks.cell_cache_off) *cells = e.cells;
+                return true;
+            }
+        return false;
+    }
+    // cells: the tables the search built for keeping (acquire), now the entry's; released where nothing is stored
+    void store(const NuSpecKey& k, const NuHooks& hooks, const double* hs, NuCellTab* cells) {
+        if (hooks.plan_cache_off) {
+            release(cells);
+            return;
         }
-    g_last_nufft_gather = gather_grid ? 1 : 0;
-    for (double& w : g_nu_work) w = 0.0;
-    g_last_cells_built = g_last_cells_reused = 0;
-    // buffers sized for the largest group
-    int64_t Bmax = 0, nfmax = 0, csmax = 0, nrow_all = 0;
-    for (const NuPlan& pl : plans) {
-        const int64_t nrow_max = std::min<int64_t>(kNuRows, pl.r1 - pl.r0);
-        const int lrow = 12 - std::min(pl.lnfft, 12);
-        Bmax = std::max<int64_t>(Bmax, (cdiv((int64_t)pl.P * nrow_max, int64_t(1) << lrow) << lrow) << pl.lnfft);
-        csmax = std::max<int64_t>(csmax, (int64_t)nharm * nrow_max * pl.nseg);
-        nfmax = std::max<int64_t>(nfmax, int64_t(1) << pl.lnfft);
-        nrow_all = std::max<int64_t>(nrow_all, nrow_max);
-    }
-    // cell-gather grids gather up to kNuGatherSet harmonics per launch, each into its own W planes
-    int gw = 1;
-    if (gather_grid) {
-        gw = std::min(nharm, kNuGatherSet);
-        while (gw > 1 && (gw + 1) * Bmax * 16 + csmax * 16 > nufft_budget()) --gw;
-    }
-    const int64_t fixed_bytes = (gw + 1) * Bmax * 16 + csmax * 16;
-    std::vector<std::pair<int, int>> passes;  // (k0, harmonics) of each MFMA spread pass
-    const int64_t ubytes = nu_spread_passes(&passes, plans, nharm, nchunk, fixed_bytes);
-    const bool generic_fft = nu_generic_fft();
-    {
-        const int rc = nu_rows_lds_attrs();
-        if (rc) return rc;
-    }
-    const char* lanes_s = getenv("CRIMP_NUFFT_LANES");
-    const int lanes_env = lanes_s ? atoi(lanes_s) : 0;
-    ARGCHK(lanes_env == 0 || lanes_env == 1 || lanes_env == 2 || lanes_env == 4 || lanes_env == 8,
-           "CRIMP_NUFFT_LANES must be 1, 2, 4 or 8");
-    int64_t starts_max = 0, starts_all = 0;  // the cell gather's start tables of the largest group, of all groups
-    std::vector<int64_t> starts_off;         // each group's tables within starts_all
-    if (gather_grid)
-        for (const NuPlan& pl : plans) {
-            int64_t tot = 0;
-            for (int k = 1; k <= nharm; ++k) tot += pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 2;
-            starts_max = std::max<int64_t>(starts_max, tot);
-            starts_off.push_back(starts_all);
-            starts_all += tot;
+        drop(k);
+        if (entries_.size() >= 16) {
+            release(&entries_.front().cells);
+            entries_.erase(entries_.begin());
         }
+        Entry e;
+        e.key = k;
+        std::memcpy(e.hs, hs, sizeof(e.hs));
+        e.cells = *cells;
+        *cells = NuCellTab{};
+        entries_.push_back(e);
+    }
+    // a search that ran an entry's plan without tables and built them for keeping: they become the entry's
+    void attach(const NuSpecKey& k, const NuHooks& hooks, NuCellTab* cells) {
+        for (Entry& e : entries_)
+            if (e.key == k && !e.cells.p && !hooks.plan_cache_off) {
+                e.cells = *cells;
+                *cells = NuCellTab{};
+                return;
+            }
+        release(cells);
+    }
+    void drop(const NuSpecKey& k) {
+        for (size_t i = 0; i < entries_.size(); ++i)
+            if (entries_[i].key == k) {
+                release(&entries_[i].cells);
+                entries_.erase(entries_.begin() + (std::ptrdiff_t)i);
+                return;
+            }
+    }
+    // room for len entries (the spare when it fits and is not more than twice too large); false: no memory, no caching
+    bool acquire(NuCellTab* t, int64_t len) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (spare_.p && (spare_.dev != dev || spare_.cap < len || spare_.cap > 2 * len + (int64_t(1) << 17))) {
+            (void)hipFree(spare_.p);
+            spare_ = NuCellTab{};
+        }
+        if (spare_.p) {
+            *t = spare_;
+            spare_ = NuCellTab{};
+        } else {
+            void* p = nullptr;
+            if (hipMalloc(&p, (size_t)len * sizeof(int64_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                return false;
+            }
+            t->p = static_cast<int64_t*>(p);
+            t->cap = len;
+            t->dev = dev;
+        }
+        t->len = len;
+        return true;
+    }
+    void release(NuCellTab* t) {
+        if (t->p) {
+            if (!spare_.p) {
+                spare_ = *t;
+            } else {
+                (void)hipFree(t->p);
+            }
+        }
+        *t = NuCellTab{};
+    }
+
+  private:
+    struct Entry {
+        NuSpecKey key;
+        double hs[5];
+        NuCellTab cells;  // none (p == nullptr): an MFMA-slot plan, tables above the cap, or the cell cache off
+    };
+    std::vector<Entry> entries_;
+    NuCellTab spare_;
+};
+static NuPlanCache g_nu_cache;
+
+// ---- the search ----
+// Z^2 / H by NUFFT over trials [first, first + count) of the fd-outer grid (shape: nf trials per row, arithmetic
+// progression with step hs[0]).
+struct NuSearchIn {
+    const double* t = nullptr;  // photon times (seconds); t0 the search's reference time: the kernels form dt = t - t0
+    double t0 = 0.0;            // as k_search_prep does (dt and dt^2 arrays are made only for a fix-up)
+    const double* freq = nullptr;
+    const double* c2 = nullptr;  // the rows' fdot terms (twod)
+    bool twod = false;
+    NuSearchShape shape;
+    NuHooks hooks;
+    const double* hs = nullptr;  // [delta, f0, dt[0], dt[n-1], unsorted flag (int bits)] (plan_nufft_search)
+    double* out = nullptr;
+    double* best = nullptr;  // crimp_search_best's [power, index], or nullptr
+    bool timed = false, no_fixup = false;
+    // [fix-up count, photons out of order (1; cell-gather plans) or a cached plan no longer valid (2), -, -, best power,
+    // best index (as doubles)], zeroed or set by k_ap_final, read back in one transfer at the end
+    int* nflag = nullptr;
+    const NuCellTab* cached = nullptr;  // a cached plan's start tables, or nullptr
+    NuCellTab* keep = nullptr;          // receives the tables this search built for the plan cache
+};
+struct NuSearchOut {
+    bool applicable = false;  // false (nothing computed): unsorted photons or an out-of-range plan, the exact rule runs
+    bool best_done = false;   // in.best holds the best trial
+    bool mismatch = false;    // a cached plan no longer holds: the caller drops it and redoes the search
+    int64_t nfixed = 0;
+};
+
+// The launches of one search, in the plan's order
+struct NuRun {
+    Scratch& sc;
+    hipStream_t s;
+    const NuSearchIn& in;
+    const NuSearchPlan& sp;
     // The start tables: the cached plan's (cells_reuse: no cell-start pass, the gathers check them), or built by this
     // search -- into memory the plan cache will own (cells_keep: every group's tables side by side) when the search
     // may be stored and they are under the cap, else into scratch, one group after the other in the same place.
-    const bool cells_reuse = gather_grid && cached && cached->p && cached->len == starts_all;
-    const bool cells_keep = gather_grid && !cells_reuse && keep && starts_all > 0 && !nu_spec_disabled() &&
-                            !nu_cell_disabled() && starts_all * (int64_t)sizeof(int64_t) <= nu_cell_cap_bytes() &&
-                            nu_cell_acquire(keep, starts_all);
+    bool cells_reuse = false, cells_keep = false;
     double* U = nullptr;
     double2 *W = nullptr, *Y = nullptr, *CS = nullptr;
-    int64_t* ctab = nullptr;
-    int64_t* cstart = nullptr;
-    int64_t* flagged = nullptr;
-    // nflag: [fix-up count, photons out of order (1; cell-gather plans) or a cached plan no longer valid (2), -, -,
-    // best power, best index (as doubles)], zeroed or set by k_ap_final, read back in one transfer at the end
-    if (!gather_grid) {
-        HIPCHK(sc.alloc(&U, (size_t)(ubytes / 8)));
-        HIPCHK(sc.alloc(&ctab, (size_t)(2 * kNuPassMax * nchunk)));
-    }
-    if (cells_reuse)
-        cstart = cached->p;  // read only
-    else if (cells_keep)
-        cstart = keep->p;
-    else if (starts_max > 0)
-        HIPCHK(sc.alloc(&cstart, (size_t)starts_max));
-    HIPCHK(sc.alloc(&W, (size_t)(Bmax * gw)));
-    HIPCHK(sc.alloc(&Y, (size_t)Bmax));
-    HIPCHK(sc.alloc(&CS, (size_t)csmax));
-    HIPCHK(sc.alloc(&flagged, (size_t)count));
-    // per-block best trials of the fused finalize (the radix-8 row pass's blocks of every row batch)
-    BestCand* best_part = nullptr;
-    int64_t best_count = 0, separate_batches = 0;
-    if (best) {
-        int64_t nb = 0;
-        for (const NuPlan& pl : plans) nb += (pl.r1 - pl.r0) * (int64_t(1) << (pl.lnfft - std::min(pl.lnfft, 12)));
-        HIPCHK(sc.alloc(&best_part, (size_t)std::max<int64_t>(nb, 1)));
-    }
-    // every MFMA (group, row batch, pass)'s slot table, uploaded once before the launches
-    std::vector<NuPass> hps;
-    for (const NuPlan& pl : plans) {
-        for (int64_t rb = pl.r0; !gather_grid && rb < pl.r1; rb += kNuRows) {
-            const int64_t SL = 2 * (int64_t)pl.P * std::min<int64_t>(kNuRows, pl.r1 - rb);
-            for (const auto& pass : passes) {
-                NuPass ps{};
-                int64_t off = 0;
-                for (int kk = 0; kk < pass.second; ++kk) {
-                    const int k = pass.first + kk;
-                    ps.gmin[kk] = pl.gmin[(size_t)(k - 1)];
-                    ps.ubase[kk] = off;
-                    off += (pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 1 + nchunk) * SL;
-                }
-                hps.push_back(ps);
-            }
-        }
-    }
+    int64_t *ctab = nullptr, *cstart = nullptr, *flagged = nullptr;
+    BestCand* best_part = nullptr;  // per-block best trials of the fused finalize
     NuPass* dps = nullptr;
-    if (!hps.empty()) {
-        HIPCHK(sc.alloc(&dps, hps.size()));
-        HIPCHK(hipMemcpyAsync(dps, hps.data(), hps.size() * sizeof(NuPass), hipMemcpyHostToDevice, s));
-    }
-    size_t ipass = 0;
-    const size_t lds_fft = (size_t)kNuTile * sizeof(double2);
-    // timed spans (CRIMP_FLAG_TIME_KERNELS): the whole pipeline, then each kernel class's sum and launch count
+    NuTables tab;
+    // timed spans (CRIMP_FLAG_TIME_KERNELS): the whole pipeline, then each kernel class's sum
     std::vector<hipEvent_t> ev;
     std::vector<int> evcls;  // class of the span ending at each mark (kNuCls*)
-    auto mark = [&]() -> hipError_t {
-        if (!timed) return hipSuccess;
+
+    NuRun(Scratch& sc_, hipStream_t s_, const NuSearchIn& in_, const NuSearchPlan& sp_) : sc(sc_), s(s_), in(in_), sp(sp_) {}
+    ~NuRun() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    hipError_t mark() {
+        if (!in.timed) return hipSuccess;
         hipEvent_t e = nullptr;
         hipError_t r = hipEventCreate(&e);
         if (r != hipSuccess) return r;
         ev.push_back(e);
         return hipEventRecord(e, s);
-    };
-    auto span = [&](int cls) -> hipError_t {
-        if (!timed) return hipSuccess;
+    }
+    hipError_t span(int cls) {
+        if (!in.timed) return hipSuccess;
         evcls.push_back(cls);
         return mark();
-    };
-    int cur_lnfft = -1;
-    NuTw T{};
-    const double2* cis = nullptr;
-    const double2* cis2 = nullptr;
-    const double* bc = nullptr;
-    size_t iplan = 0;
-    for (const NuPlan& pl : plans) {
-        const size_t ip = iplan++;
-        if (pl.lnfft != cur_lnfft) {  // tables for this group's n (a group's first launch follows their upload)
-            const int rc = nu_tables(sc, s, pl.lnfft, &T, &cis, &bc, &cis2);
-            if (rc) return rc;
-            cur_lnfft = pl.lnfft;
+    }
+
+    int alloc() {
+        if (!sp.gather) {
+            HIPCHK(sc.alloc(&U, (size_t)(sp.ubytes / 8)));
+            HIPCHK(sc.alloc(&ctab, (size_t)(2 * kNuPassMax * sp.nchunk)));
         }
-        if (ev.empty()) HIPCHK(mark());
-        const int lnfft = pl.lnfft, P = pl.P;
-        const int64_t nfft = int64_t(1) << lnfft;
-        // FFT shape: one row pass for n <= kNuTile, else columns (n1 = n / 4096 <= 4096) then rows of 4096
-        const int ln2 = std::min(lnfft, 12), ln1 = lnfft - ln2;
-        const int lcol = 12 - ln1;  // columns per block in pass 1 (n1 * c = 4096)
-        const int64_t jbase = pl.j0 + pl.h;
-        auto occupied = [&](int k, int* alo, int* acnt) {
-            nu_occupied(pl.gmin[(size_t)(k - 1)], pl.gmax[(size_t)(k - 1)], lnfft, ln1, alo, acnt);
-        };
-        // the radix-8 row kernels (rows of 2048 and 4096) finalize in the last harmonic's launch (NuFinal)
-        const bool fuse_final = ln2 >= 11 && !generic_fft && !nu_final_separate();
-        bool final_done = false;  // set by fft_combine when it finalized the batch
-        // W (moments of harmonic k, rows [rb, rb + nrow)) -> FFT -> (C_k, S_k) of the batch's trials: columns by ln1,
-        // rows by ln2, the generic kernel of each wherever no specialised one exists (or generic_fft)
-        auto fft_combine = [&](int k, int64_t rb, int nrow, int64_t tb0, int64_t nbt, const double2* W) -> int {
-            const int64_t Bp = (int64_t)P * nrow;
-            const double plane = 16.0 * (double)Bp * (double)nfft;  // one complex FFT buffer of the batch
-            const double2* Z = W;
-            if (ln1 > 0) {
-                int alo = 0, acnt = 0;
-                occupied(k, &alo, &acnt);
-                g_nu_work[kNuClsPass1] += plane * ((double)acnt / (double)(int64_t(1) << ln1)) + plane;  // occupied rows in, all out
-                if (ln1 == 8 && !generic_fft) {
-                    const int64_t ngroups = Bp << (ln2 - 4);
-                    k_nu_cols256<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 256, lds_fft, s>>>(
-                        W, Y, lnfft, T, alo, acnt, ngroups);
-                } else if (ln1 == 9 && !generic_fft) {
-                    const int64_t ngroups = Bp << (ln2 - 3);
-                    k_nu_cols512<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 512, lds_fft, s>>>(
-                        W, Y, lnfft, T, alo, acnt, ngroups);
-                } else {
-                    k_nu_fft_cols<<<dim3((unsigned)(int64_t(1) << (ln2 - lcol)), (unsigned)Bp), 256, lds_fft, s>>>(
-                        W, Y, lnfft, ln1, lcol, T, alo, acnt);
-                }
-                HIPCHK(hipGetLastError());
-                Z = Y;
-                HIPCHK(span(kNuClsPass1));
-            }
-            NuFinal F{};
-            if (fuse_final && k == nharm) {
-                F.on = 1;
-                F.m = nharm;
-                F.stat = stat;
-                F.Pc = P;
-                F.nph = (double)n;
-                F.invfact = pl.invfact;
-                F.rel = fixup_rel();
-                F.tb0 = tb0;
-                F.out = out;
-                F.nflag = nflag;
-                F.flagged = flagged;
-                F.best_part = best ? best_part : nullptr;
-                F.best_base = best_count;
-                F.CS0 = CS;
-                best_count += (int64_t(1) << ln1) * nrow;
-                final_done = true;
-            }
-            // bytes: the moments' planes read; the sums written, or (fused finalize) the earlier harmonics' sums read
-            // and the powers written
-            g_nu_work[kNuClsPass2] += plane + (F.on ? (16.0 * (nharm - 1) + 8.0) * (double)nbt : 16.0 * (double)nbt);
-            const dim3 g2((unsigned)(int64_t(1) << ln1), (unsigned)nrow);
-            const int64_t jhi = pl.nseg - 1 - pl.h, tbase = rb * nf + jbase - (tb0 + first);
-            double2* CSk = CS + (int64_t)(k - 1) * nbt;
-            // plo = 0, accum = 0: all P moments in the one launch, the sum from zero (see the row kernels' comment)
-            if (ln2 == 12 && !generic_fft)
-                k_nu_rows_iw<<<g2, 512, 2 * lds_fft, s>>>(Z, lnfft, P, 0, 0, nrow, nf, jhi, pl.h, tbase, nbt, bc, CSk, F);
-            else if (ln2 == 11 && !generic_fft)
-                k_nu_rows_combine8<11><<<g2, 256, nu_rows_lds(11), s>>>(Z, lnfft, P, 0, 0, nrow, nf, jhi, pl.h, tbase, nbt,
-                                                                         bc, CSk, F);
+        if (cells_reuse)
+            cstart = in.cached->p;  // read only
+        else if (cells_keep)
+            cstart = in.keep->p;
+        else if (sp.starts_max > 0)
+            HIPCHK(sc.alloc(&cstart, (size_t)sp.starts_max));
+        HIPCHK(sc.alloc(&W, (size_t)(sp.Bmax * sp.gw)));
+        HIPCHK(sc.alloc(&Y, (size_t)sp.Bmax));
+        HIPCHK(sc.alloc(&CS, (size_t)sp.csmax));
+        HIPCHK(sc.alloc(&flagged, (size_t)in.shape.count));
+        if (sp.best_alloc > 0) HIPCHK(sc.alloc(&best_part, (size_t)sp.best_alloc));
+        if (!sp.passes.empty()) {
+            HIPCHK(sc.alloc(&dps, sp.passes.size()));
+            HIPCHK(hipMemcpyAsync(dps, sp.passes.data(), sp.passes.size() * sizeof(NuPass), hipMemcpyHostToDevice, s));
+        }
+        return CRIMP_OK;
+    }
+
+    // The group's start tables. No zeroing: on time-sorted photons every entry is written (each cell's first photon
+    // writes it), and on unsorted ones the gathers read none of them (k_nu_gather exits on *bad).
+    int cell_starts(const NuGroup& g, int64_t base) {
+        const int64_t n = in.shape.n;
+        for (const NuCellLaunch& cl : g.cells) {
+            NuCellArgs ca = cl.args;
+            for (int j = 0; j < cl.nk; ++j) ca.off[j] += base;
+            const unsigned cb = (unsigned)std::min<int64_t>(cdiv(cdiv(n, 2), 256 * kNuCellU), 2048);
+            if ((reinterpret_cast<uintptr_t>(in.t) & 15u) == 0)
+                k_nu_cellstart<true><<<cb, 256, 0, s>>>(in.t, in.t0, n, g.pl.s1, cl.k0, cl.nk, ca, cstart, in.nflag + 1);
             else
-                k_nu_fft_rows_combine<<<g2, 256, lds_fft, s>>>(Z, ln2, lnfft, P, nrow, nf, jhi, pl.h, tbase, nbt, bc, CSk);
+                k_nu_cellstart<false><<<cb, 256, 0, s>>>(in.t, in.t0, n, g.pl.s1, cl.k0, cl.nk, ca, cstart, in.nflag + 1);
             HIPCHK(hipGetLastError());
-            HIPCHK(span(kNuClsPass2));
-            return CRIMP_OK;
-        };
-        auto finalize =[&](int64_t tb0, int64_t nbt) -> int {
-            g_nu_work[kNuClsFinalize] += 16.0 * (double)nharm * (double)nbt + 8.0 * (double)nbt;
-            k_nu_finalize<<<(unsigned)cdiv(nbt, 256), 256, 0, s>>>(CS, nbt, nharm, stat, (double)n, nf, jbase, nfft, P,
-                                                                   pl.invfact, fixup_rel(), tb0, first, out, nflag,
-                                                                   flagged);
+        }
+        HIPCHK(span(kNuClsCellStart));
+        return CRIMP_OK;
+    }
+
+    // one gather launch, then the FFT of each of its harmonics
+    int gather_set(const NuGroup& g, const NuBatch& b, const NuGatherSet& set, int64_t base) {
+        const NuPlan& pl = g.pl;
+        NuGatherSet S = set;
+        for (int jj = 0; jj < S.nk; ++jj) S.soff[jj] += base;
+        launch_gather(in.twod, cells_reuse, S.blk0[S.nk], in.t, in.t0, cstart, int64_t(1) << pl.lnfft, pl.s1, pl.fch,
+                      pl.fcl, in.twod ? in.c2 + b.rb : nullptr, b.nrow, pl.P, S, in.nflag + 1, tab.cis2, W, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(span(kNuClsSpread));
+        for (int jj = 0; jj < S.nk; ++jj) {
+            const int rc = fft_combine(g, b, S.k[jj], W + S.woff[jj]);
+            if (rc) return rc;
+        }
+        return CRIMP_OK;
+    }
+
+    // one MFMA spread launch, then the merge and the FFT of each of its harmonics <= nharm
+    int mfma_pass(const NuGroup& g, const NuBatch& b, const NuMfmaPass& mp) {
+        const NuPlan& pl = g.pl;
+        const int64_t n = in.shape.n, nchunk = sp.nchunk, nfft = int64_t(1) << pl.lnfft;
+        const int64_t SL = 2 * (int64_t)pl.P * b.nrow;
+        const NuPass& ps = sp.passes[mp.ipass];
+        const NuPass* dp = dps + mp.ipass;
+        const dim3 grid((unsigned)cdiv(nchunk, kNuWaves));
+        if (in.twod)
+            nu_launch_spread<true>(mp.gl, grid, s, in.t, in.t0, n, nchunk, pl.s1, pl.fch, pl.fcl, in.c2 + b.rb, b.nrow,
+                                   mp.k0, pl.P, dp, tab.cis, U, ctab, in.nflag + 1);
+        else
+            nu_launch_spread<false>(mp.gl, grid, s, in.t, in.t0, n, nchunk, pl.s1, pl.fch, pl.fcl, in.c2 + b.rb, b.nrow,
+                                    mp.k0, pl.P, dp, tab.cis, U, ctab, in.nflag + 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(span(kNuClsSpread));
+        for (int kk = 0; kk < mp.gl && mp.k0 + kk <= in.shape.nharm; ++kk) {
+            const int k = mp.k0 + kk;
+            int alo = 0, acnt = 0;
+            nu_occupied(pl.gmin[(size_t)(k - 1)], pl.gmax[(size_t)(k - 1)], pl.lnfft, g.ln1, &alo, &acnt);
+            const int64_t gbase = (int64_t)alo << g.ln2, gcount = (int64_t)acnt << g.ln2;
+            k_nu_merge<<<(unsigned)cdiv(gcount, kNuMergeG), 256, (size_t)kNuMergeG * SL * sizeof(double), s>>>(
+                U + ps.ubase[kk], SL, ctab + 2 * kk * nchunk, nchunk, ps.gmin[kk], pl.gmax[(size_t)(k - 1)], nfft, gbase,
+                gcount, W, in.nflag + 1);
             HIPCHK(hipGetLastError());
-            HIPCHK(span(kNuClsFinalize));
-            return CRIMP_OK;
-        };
-        if (gather_grid) {
-            std::vector<int64_t> soff((size_t)nharm);
-            int64_t off = cells_reuse || cells_keep ? starts_off[ip] : 0;
-            // no zeroing of the start tables: on time-sorted photons every entry is written (each cell's first
-            // photon writes it), and on unsorted ones the gathers read none of them (k_nu_gather exits on *bad)
-            for (int k0 = 1; k0 <= nharm; k0 += kNuCellK) {
-                NuCellArgs ca{};
-                const int nk = std::min(kNuCellK, nharm - k0 + 1);
-                for (int j = 0; j < nk; ++j) {
-                    const int k = k0 + j;
-                    ca.gmin[j] = pl.gmin[(size_t)(k - 1)];
-                    ca.span[j] = pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 1;
-                    ca.off[j] = off;
-                    soff[(size_t)(k - 1)] = off;
-                    off += ca.span[j] + 1;
-                }
-                if (cells_reuse) continue;  // the layout only
-                const unsigned cb = (unsigned)std::min<int64_t>(cdiv(cdiv(n, 2), 256 * kNuCellU), 2048);
-                if ((reinterpret_cast<uintptr_t>(t) & 15u) == 0)
-                    k_nu_cellstart<true><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1);
-                else
-                    k_nu_cellstart<false><<<cb, 256, 0, s>>>(t, t0, n, pl.s1, k0, nk, ca, cstart, nflag + 1);
-                HIPCHK(hipGetLastError());
-            }
-            if (cells_reuse) {
-                g_last_cells_reused += nharm;
+            HIPCHK(span(kNuClsMerge));
+            const int rc = fft_combine(g, b, k, W);
+            if (rc) return rc;
+        }
+        return CRIMP_OK;
+    }
+
+    // Wk (moments of harmonic k, the batch's rows) -> FFT -> (C_k, S_k) of the batch's trials: columns by ln1, rows by
+    // ln2, the generic kernel of each wherever no specialised one exists (or generic_fft); the last harmonic's launch of
+    // a fuse_final group finalizes the batch (NuFinal)
+    int fft_combine(const NuGroup& g, const NuBatch& b, int k, const double2* Wk) {
+        const NuPlan& pl = g.pl;
+        const NuSearchShape& sh = in.shape;
+        const bool generic_fft = in.hooks.generic_fft;
+        const int lnfft = pl.lnfft, P = pl.P, ln1 = g.ln1, ln2 = g.ln2;
+        const size_t lds_fft = (size_t)kNuTile * sizeof(double2);
+        const int64_t Bp = (int64_t)P * b.nrow;
+        const double2* Z = Wk;
+        if (ln1 > 0) {
+            const int lcol = 12 - ln1;  // columns per block in pass 1 (n1 * c = 4096)
+            int alo = 0, acnt = 0;
+            nu_occupied(pl.gmin[(size_t)(k - 1)], pl.gmax[(size_t)(k - 1)], lnfft, ln1, &alo, &acnt);
+            if (ln1 == 8 && !generic_fft) {
+                const int64_t ngroups = Bp << (ln2 - 4);
+                k_nu_cols256<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 256, lds_fft, s>>>(
+                    Wk, Y, lnfft, tab.T, alo, acnt, ngroups);
+            } else if (ln1 == 9 && !generic_fft) {
+                const int64_t ngroups = Bp << (ln2 - 3);
+                k_nu_cols512<<<(unsigned)std::min<int64_t>(ngroups, 2 * nu_cus()), 512, lds_fft, s>>>(
+                    Wk, Y, lnfft, tab.T, alo, acnt, ngroups);
             } else {
-                g_last_cells_built += nharm;
-                HIPCHK(span(kNuClsCellStart));
+                k_nu_fft_cols<<<dim3((unsigned)(int64_t(1) << (ln2 - lcol)), (unsigned)Bp), 256, lds_fft, s>>>(
+                    Wk, Y, lnfft, ln1, lcol, tab.T, alo, acnt);
             }
-            for (int64_t rb = pl.r0; rb < pl.r1; rb += kNuGatherRows) {
-                const int nrow = (int)std::min<int64_t>(kNuGatherRows, pl.r1 - rb);
-                const int64_t tb0 = std::max<int64_t>(first, rb * nf) - first;
-                const int64_t nbt = std::min<int64_t>(first + count, (rb + nrow) * nf) - first - tb0;
-                for (int k0 = 1; k0 <= nharm; k0 += gw) {
-                    NuGatherSet S{};
-                    S.nk = std::min(gw, nharm - k0 + 1);
-                    int64_t blocks = 0, set_cells = 0;  // the set's occupied cells (threads at one lane per cell)
-                    for (int jj = 0; jj < S.nk; ++jj) {
-                        int alo = 0, acnt = 0;
-                        occupied(k0 + jj, &alo, &acnt);
-                        set_cells += (int64_t)acnt << ln2;
-                    }
-                    for (int jj = 0; jj < S.nk; ++jj) {
-                        const int k = k0 + jj;
-                        int alo = 0, acnt = 0;
-                        occupied(k, &alo, &acnt);
-                        const int64_t gbase = (int64_t)alo << ln2, gcount = (int64_t)acnt << ln2;
-                        // lanes per cell: doubled (up to 4) while the launch's threads stay <= 2^20 -- counted over
-                        // every harmonic of the set at the doubled lanes -- and each lane keeps >= 8 photons (config
-                        // 3, both harmonics in one launch: 0.099 ms at 2 lanes, 0.108 at 4, 0.143 at 8,
-                        // profiles/r06/ab_gather_lanes.log)
-                        const int64_t kspan = pl.gmax[(size_t)(k - 1)] - pl.gmin[(size_t)(k - 1)] + 1;
-                        const int64_t ppc = n / std::max<int64_t>(1, std::min<int64_t>(kspan, nfft));
-                        int L = 1;
-                        while (L < 4 && set_cells * 2 * L <= (int64_t(1) << 20) && ppc >= 4 * 2 * L) L *= 2;
-                        if (lanes_env > 0) L = lanes_env;  // test hook: CRIMP_NUFFT_LANES=1|2|4|8
-                        S.k[jj] = k;
-                        S.lanes_log2[jj] = L == 8 ? 3 : L == 4 ? 2 : L == 2 ? 1 : 0;
-                        S.blk0[jj] = blocks;
-                        blocks += cdiv(gcount * L, 256);
-                        S.gmin[jj] = pl.gmin[(size_t)(k - 1)];
-                        S.gmax[jj] = pl.gmax[(size_t)(k - 1)];
-                        S.gbase[jj] = gbase;
-                        S.gcount[jj] = gcount;
-                        S.soff[jj] = soff[(size_t)(k - 1)];
-                        S.woff[jj] = (int64_t)jj * Bmax;
-                        // per photon and row: premultiplier phase + cis ~ 40 flops, then 2 FMA + 1 multiply per moment
-                        g_nu_work[0] += (40.0 + 5.0 * P) * (double)n * nrow;
-                        g_nu_work[kNuClsSpread] += 8.0 * (double)n + 16.0 * (double)P * nrow * (double)gcount;
-                    }
-                    S.blk0[S.nk] = blocks;
-                    launch_gather(twod, cells_reuse, blocks, t, t0, cstart, nfft, pl.s1, pl.fch, pl.fcl,
-                                  twod ? c2 + rb : nullptr, nrow, P, S, nflag + 1, cis2, W, s);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(span(kNuClsSpread));
-                    for (int jj = 0; jj < S.nk; ++jj) {
-                        int rc = fft_combine(k0 + jj, rb, nrow, tb0, nbt, W + (int64_t)jj * Bmax);
-                        if (rc) return rc;
-                    }
-                }
-                if (final_done) {
-                    final_done = false;
-                    continue;
-                }
-                ++separate_batches;
-                int rc = finalize(tb0, nbt);
+            HIPCHK(hipGetLastError());
+            Z = Y;
+            HIPCHK(span(kNuClsPass1));
+        }
+        NuFinal F{};
+        if (g.fuse_final && k == sh.nharm) {
+            F.on = 1;
+            F.m = sh.nharm;
+            F.stat = sh.stat;
+            F.Pc = P;
+            F.nph = (double)sh.n;
+            F.invfact = pl.invfact;
+            F.rel = fixup_rel();
+            F.tb0 = b.tb0;
+            F.out = in.out;
+            F.nflag = in.nflag;
+            F.flagged = flagged;
+            F.best_part = in.best ? best_part : nullptr;
+            F.best_base = b.best_base;
+            F.CS0 = CS;
+        }
+        const dim3 g2((unsigned)(int64_t(1) << ln1), (unsigned)b.nrow);
+        const int64_t jhi = pl.nseg - 1 - pl.h, tbase = b.rb * sh.nf + g.jbase - (b.tb0 + sh.first);
+        double2* CSk = CS + (int64_t)(k - 1) * b.nbt;
+        // plo = 0, accum = 0: all P moments in the one launch, the sum from zero (see the row kernels' comment)
+        if (ln2 == 12 && !generic_fft)
+            k_nu_rows_iw<<<g2, 512, 2 * lds_fft, s>>>(Z, lnfft, P, 0, 0, b.nrow, sh.nf, jhi, pl.h, tbase, b.nbt, tab.bc,
+                                                      CSk, F);
+        else if (ln2 == 11 && !generic_fft)
+            k_nu_rows_combine8<11><<<g2, 256, nu_rows_lds(11), s>>>(Z, lnfft, P, 0, 0, b.nrow, sh.nf, jhi, pl.h, tbase,
+                                                                     b.nbt, tab.bc, CSk, F);
+        else
+            k_nu_fft_rows_combine<<<g2, 256, lds_fft, s>>>(Z, ln2, lnfft, P, b.nrow, sh.nf, jhi, pl.h, tbase, b.nbt,
+                                                           tab.bc, CSk);
+        HIPCHK(hipGetLastError());
+        HIPCHK(span(kNuClsPass2));
+        return CRIMP_OK;
+    }
+
+    int finalize(const NuGroup& g, const NuBatch& b) {
+        const NuSearchShape& sh = in.shape;
+        k_nu_finalize<<<(unsigned)cdiv(b.nbt, 256), 256, 0, s>>>(CS, b.nbt, sh.nharm, sh.stat, (double)sh.n, sh.nf, g.jbase,
+                                                                 int64_t(1) << g.pl.lnfft, g.pl.P, g.pl.invfact,
+                                                                 fixup_rel(), b.tb0, sh.first, in.out, in.nflag, flagged);
+        HIPCHK(hipGetLastError());
+        HIPCHK(span(kNuClsFinalize));
+        return CRIMP_OK;
+    }
+
+    // every group: its tables, its start tables, then batch by batch spread -> FFT -> finalize
+    int launch_all() {
+        int cur_lnfft = -1;
+        for (const NuGroup& g : sp.groups) {
+            int rc = CRIMP_OK;
+            if (g.pl.lnfft != cur_lnfft) {  // tables for this group's n (a group's first launch follows their upload)
+                rc = nu_tables(s, g.pl.lnfft, &tab);
+                if (rc) return rc;
+                cur_lnfft = g.pl.lnfft;
+            }
+            if (ev.empty()) HIPCHK(mark());
+            const int64_t base = cells_reuse || cells_keep ? g.starts_off : 0;
+            if (sp.gather && !cells_reuse) {
+                rc = cell_starts(g, base);
                 if (rc) return rc;
             }
-            continue;
-        }
-        for (int64_t rb = pl.r0; rb < pl.r1; rb += kNuRows) {
-            const int nrow = (int)std::min<int64_t>(kNuRows, pl.r1 - rb);
-            const int64_t tb0 = std::max<int64_t>(first, rb * nf) - first;
-            const int64_t tb1 = std::min<int64_t>(first + count, (rb + nrow) * nf) - first;
-            const int64_t nbt = tb1 - tb0;
-            const int64_t SL = 2 * (int64_t)P * nrow;
-            for (const auto& pass : passes) {
-                const int k0 = pass.first, gl = pass.second;
-                const NuPass& ps = hps[ipass];
-                const NuPass* dp = dps + ipass++;
-                dim3 grid((unsigned)cdiv(nchunk, kNuWaves));
-                // issued: one 16x16x4 f64 MFMA (2048 flops) per 4 photons and harmonic; slots written
-                g_nu_work[0] += 512.0 * (double)n * gl;
-                g_nu_work[kNuClsSpread] += 8.0 * (double)n;
-                for (int kk = 0; kk < gl; ++kk)
-                    g_nu_work[kNuClsSpread] += 8.0 * (double)SL *
-                                    (double)(pl.gmax[(size_t)(k0 + kk - 1)] - ps.gmin[kk] + 1 + nchunk);
-                if (twod)
-                    nu_launch_spread<true>(gl, grid, s, t, t0, n, nchunk, pl.s1, pl.fch, pl.fcl, c2 + rb, nrow, k0, P, dp, cis,
-                                           U, ctab, nflag + 1);
-                else
-                    nu_launch_spread<false>(gl, grid, s, t, t0, n, nchunk, pl.s1, pl.fch, pl.fcl, c2 + rb, nrow, k0, P, dp,
-                                            cis, U, ctab, nflag + 1);
-                HIPCHK(hipGetLastError());
-                HIPCHK(span(kNuClsSpread));
-                for (int kk = 0; kk < gl && k0 + kk <= nharm; ++kk) {
-                    const int k = k0 + kk;
-                    int alo = 0, acnt = 0;
-                    occupied(k, &alo, &acnt);
-                    const int64_t gbase = (int64_t)alo << ln2, gcount = (int64_t)acnt << ln2;
-                    g_nu_work[kNuClsMerge] += 8.0 * (double)SL * (double)(pl.gmax[(size_t)(k - 1)] - ps.gmin[kk] + 1 + nchunk) +
-                                    16.0 * (double)P * nrow * (double)gcount;
-                    k_nu_merge<<<(unsigned)cdiv(gcount, kNuMergeG), 256, (size_t)kNuMergeG * SL * sizeof(double), s>>>(
-                        U + ps.ubase[kk], SL, ctab + 2 * kk * nchunk, nchunk, ps.gmin[kk], pl.gmax[(size_t)(k - 1)],
-                        nfft, gbase, gcount, W, nflag + 1);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(span(kNuClsMerge));
-                    int rc = fft_combine(k, rb, nrow, tb0, nbt, W);
+            for (const NuBatch& b : g.batches) {
+                for (const NuGatherSet& S : b.sets) {
+                    rc = gather_set(g, b, S, base);
                     if (rc) return rc;
                 }
+                for (const NuMfmaPass& mp : b.mfma) {
+                    rc = mfma_pass(g, b, mp);
+                    if (rc) return rc;
+                }
+                if (g.fuse_final) continue;
+                rc = finalize(g, b);
+                if (rc) return rc;
             }
-            if (final_done) {
-                final_done = false;
-                continue;
-            }
-            ++separate_batches;
-            int rc = finalize(tb0, nbt);
-            if (rc) return rc;
         }
+        return CRIMP_OK;
     }
-    if (timed) {
+
+    // the whole pipeline's ms, then the classes' ms, then their launch counts (the plan's)
+    int report_times() {
+        if (!in.timed) return CRIMP_OK;
         HIPCHK(hipEventSynchronize(ev.back()));
         float tot = 0.0f;
-        double cls[kNuCls] = {0, 0, 0, 0, 0, 0, 0}, cnt[kNuCls] = {0, 0, 0, 0, 0, 0, 0};
+        double cls[kNuCls] = {0, 0, 0, 0, 0, 0, 0};
         HIPCHK(hipEventElapsedTime(&tot, ev.front(), ev.back()));
         for (size_t i = 1; i < ev.size(); ++i) {
             float ms = 0.0f;
             HIPCHK(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
             cls[evcls[i - 1]] += ms;
-            cnt[evcls[i - 1]] += 1.0;  // launches: one per span except the cell starts (one span per nharm launches)
         }
-        cnt[kNuClsCellStart] *= (nharm + kNuCellK - 1) / kNuCellK;
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         if (g_kernel_times.empty()) g_last_kernel_ms = tot;
-        g_kernel_times.push_back(tot);  // then the classes' ms, then their launch counts
+        g_kernel_times.push_back(tot);
         for (double v : cls) g_kernel_times.push_back(v);
-        for (double v : cnt) g_kernel_times.push_back(v);
+        for (int c = 0; c < kNuCls; ++c)
+            g_kernel_times.push_back(c == kNuClsCellStart && cells_reuse ? 0.0 : (double)sp.launches[c]);
+        return CRIMP_OK;
     }
+};
+
+static int nufft_search(Scratch& sc, hipStream_t s, const NuSearchIn& in, NuSearchOut* res) {
+    *res = NuSearchOut{};
+    const NuSearchShape& sh = in.shape;
+    const NuSearchPlan sp = plan_nufft_search(in.hs, sh, in.hooks);
+    if (!sp.applicable) return CRIMP_OK;
+    res->applicable = true;
+    g_last_search_path = 2;
+    g_last_nufft_n = sp.last_n;
+    g_last_nufft_p = sp.last_p;
+    g_last_nufft_gather = sp.gather ? 1 : 0;
+    std::memcpy(g_nu_work, sp.work, sizeof(g_nu_work));
+    g_last_cells_built = g_last_cells_reused = 0;
+    {
+        const int rc = nu_rows_lds_attrs();
+        if (rc) return rc;
+    }
+    ARGCHK(in.hooks.lanes_valid(), "CRIMP_NUFFT_LANES must be 1, 2, 4 or 8");
+    NuRun run(sc, s, in, sp);
+    run.cells_reuse = sp.gather && in.cached && in.cached->p && in.cached->len == sp.starts_all;
+    run.cells_keep = sp.gather && !run.cells_reuse && in.keep && sp.starts_all > 0 && !in.hooks.plan_cache_off &&
+                     !in.hooks.cell_cache_off && sp.starts_all * (int64_t)sizeof(int64_t) <= in.hooks.cell_cap &&
+                     g_nu_cache.acquire(in.keep, sp.starts_all);
+    (run.cells_reuse ? g_last_cells_reused : g_last_cells_built) = sp.cell_tables;
+    int rc = run.alloc();
+    if (!rc) rc = run.launch_all();
+    if (!rc) rc = run.report_times();
+    if (rc) return rc;
     // the best trial of the powers (crimp_search_best) rides on the same read-back; valid unless a fix-up follows
-    if (best) {
-        if (separate_batches == 0 && best_count > 0) {  // every batch finalized in its row pass: reduce their blocks
-            k_best_final<<<1, 256, 0, s>>>(best_part, (int)best_count, reinterpret_cast<double*>(nflag + 4));
+    if (in.best) {
+        if (sp.separate_batches == 0 && sp.best_count > 0) {  // every batch finalized in its row pass: reduce their blocks
+            k_best_final<<<1, 256, 0, s>>>(run.best_part, (int)sp.best_count, reinterpret_cast<double*>(in.nflag + 4));
             HIPCHK(hipGetLastError());
         } else {
-            const int rc = launch_best(sc, s, out, count, reinterpret_cast<double*>(nflag + 4));
+            rc = launch_best(sc, s, in.out, sh.count, reinterpret_cast<double*>(in.nflag + 4));
             if (rc) return rc;
         }
     }
     int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(d2h(s, fl, nflag, (best ? 8 : 2) * sizeof(int)));
+    HIPCHK(d2h(s, fl, in.nflag, (in.best ? 8 : 2) * sizeof(int)));
     if (fl[1]) {  // photons out of order (found by the cell starts), or a cached plan that no longer holds (2):
-        *applicable = false;  // nothing computed, the default path (or a fresh plan) runs
-        *mismatch = (fl[1] & 2) != 0;
+        res->applicable = false;  // nothing computed, the default path (or a fresh plan) runs
+        res->mismatch = (fl[1] & 2) != 0;
         g_last_search_path = 0;
         return CRIMP_OK;
     }
     const int nf_h = fl[0];
-    *nfixed = nf_h;
-    if (best && (nf_h == 0 || no_fixup)) {
-        std::memcpy(best, fl + 4, 2 * sizeof(double));
-        *best_done = true;
+    res->nfixed = nf_h;
+    if (in.best && (nf_h == 0 || in.no_fixup)) {
+        std::memcpy(in.best, fl + 4, 2 * sizeof(double));
+        res->best_done = true;
     }
-    if (nf_h == 0 || no_fixup) return CRIMP_OK;
+    if (nf_h == 0 || in.no_fixup) return CRIMP_OK;
     double *dt = nullptr, *dt2 = nullptr;  // the fix-up's fp64 kernel reads dt (and dt^2) arrays
-    HIPCHK(sc.alloc(&dt, (size_t)n));
-    if (twod) HIPCHK(sc.alloc(&dt2, (size_t)n));
-    k_search_prep<<<(int)std::min<int64_t>(cdiv(n, 256), 4096), 256, 0, s>>>(t, n, t0, dt, dt2);
+    HIPCHK(sc.alloc(&dt, (size_t)sh.n));
+    if (in.twod) HIPCHK(sc.alloc(&dt2, (size_t)sh.n));
+    k_search_prep<<<(int)std::min<int64_t>(cdiv(sh.n, 256), 4096), 256, 0, s>>>(in.t, sh.n, in.t0, dt, dt2);
     HIPCHK(hipGetLastError());
-    return fixup_search(sc, s, dt, dt2, n, freq, nf, c2, twod, nharm, stat, first, flagged, nf_h, out);
+    return fixup_search(sc, s, dt, dt2, sh.n, in.freq, sh.nf, in.c2, in.twod, sh.nharm, sh.stat, sh.first, run.flagged, nf_h,
+                        in.out);
 }
