@@ -35,6 +35,8 @@ MODEL_IDS = {"fourier": 0, "cauchy": 1, "vonmises": 2}
 MAX_GLITCH = 32
 MAX_WAVE = 64
 MAX_COMP = 16
+BINARY_NONE, BINARY_BT, BINARY_ELL1 = 0, 1, 2
+PART_EMISSION = 8
 
 CUBE_Y_OPEN_LAST = 1
 CUBE_Z_OPEN_LAST = 2
@@ -53,7 +55,12 @@ class TimingModel(ctypes.Structure):
     _fields_ = [("pepoch", ctypes.c_double), ("f", ctypes.c_double * 13), ("n_glitch", ctypes.c_int32),
                 ("glitch", (ctypes.c_double * 7) * MAX_GLITCH), ("n_wave", ctypes.c_int32),
                 ("wave_epoch", ctypes.c_double), ("wave_om", ctypes.c_double),
-                ("wave_ab", (ctypes.c_double * 2) * MAX_WAVE)]
+                ("wave_ab", (ctypes.c_double * 2) * MAX_WAVE),
+                # the binary orbit; a zero tail is "no binary" (include/crimp_hip.h)
+                ("binary", ctypes.c_int32), ("bin_pb", ctypes.c_double), ("bin_pbdot", ctypes.c_double),
+                ("bin_a1dot", ctypes.c_double), ("bin_a1", ctypes.c_double), ("bin_t0", ctypes.c_double),
+                ("bin_ecc", ctypes.c_double), ("bin_om", ctypes.c_double), ("bin_omdot", ctypes.c_double),
+                ("bin_gamma", ctypes.c_double), ("bin_eps1", ctypes.c_double), ("bin_eps2", ctypes.c_double)]
 
 
 SHAPE_SUMS = 4 + 3 * MAX_COMP  # CRIMP_SHAPE_SUMS
@@ -92,7 +99,7 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_device_count", "crimp_calcphase", "crimp_search", "crimp_search_best", "crimp_best", "crimp_search_sets", "crimp_toa_points",
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
-           "crimp_gather_ranges", "crimp_sim_events")
+           "crimp_gather_ranges", "crimp_sim_events", "crimp_binary_delay")
 
 _lib = None
 _lock = threading.Lock()
@@ -144,6 +151,7 @@ def load(require_device=True):
             L.crimp_sim_events.argtypes = [MP, ctypes.POINTER(SimShape), ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, P, i64, ctypes.c_uint64, i64, i64, P, P, i64,
                                            ctypes.POINTER(i64), ctypes.c_double, u32, P]
+            L.crimp_binary_delay.argtypes = [P, i64, MP, P, P, u32, P]
             L.crimp_toa_redchi2.argtypes = [P, P, i64, ctypes.POINTER(Template), P, P, P, P, i32, i32, P, u32, P]
             L.crimp_toa_fit_redchi2.argtypes = [P, P, i64, ctypes.POINTER(Template), P, ctypes.c_double, i32, i32, P, P,
                                                 i32, i32, P, P, u32, P]

@@ -60,6 +60,12 @@ class Phases:
             return 0 * self.timModParam["F0"]
         return self._run(PART_WAVES)
 
+    def binarydelay(self):
+        """The orbital delay (s) of every time under the model's BINARY (crimp_amd.binarymodels.binary_delay; not in
+        the reference). With an orbit, the three parts above and calcphase() are evaluated at the emission time."""
+        from .binarymodels import binary_delay
+        return binary_delay(self.timeMJD, self.timModParam)
+
 
 def calcphase(timeMJD, timMod):
     """(total phase, cycle-folded phase in [0,1)) -- calcphase.py:152-176."""

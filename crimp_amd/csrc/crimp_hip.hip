@@ -377,6 +377,8 @@ __device__ __forceinline__ void sincos_rev_poly(float r, float& s, float& c) {
     c = ((iq + 1) & 2) ? -c_a : c_a;
 }
 
+#include "binary_delay.h"
+
 // ============================================================== 3. calcphase
 struct CPModel {
     double pepoch;
@@ -391,11 +393,32 @@ struct CPModel {
 };
 static_assert(sizeof(CPModel) + 64 <= 4096, "CPModel is passed by value in the kernel arguments (4 KB limit)");
 
-__device__ __forceinline__ double cp_one(const CPModel* __restrict__ M, double t) {
+// The model as a kernel argument. BIN = false is CPModel alone, the layout and the code of a build without binary
+// orbits; BIN = true appends the orbit, and the kernel's phase is the one at the emission time (parts bit 3).
+template <bool BIN>
+struct CPArgs;
+template <>
+struct CPArgs<false> {
+    CPModel m;
+};
+template <>
+struct CPArgs<true> {
+    CPModel m;
+    BinModel b;
+};
+static_assert(sizeof(CPArgs<false>) == sizeof(CPModel), "the non-binary kernels take CPModel as before");
+static_assert(sizeof(CPArgs<true>) % 8 == 0 && sizeof(CPArgs<true>) + 64 <= 4096,
+              "the model and the orbit ride in the kernel arguments (4 KB limit)");
+
+// BIN: tau (s) is the orbital delay of t, and every part is evaluated at the emission time t - tau / 86400. tau
+// enters each part in seconds after the epoch difference -- never through an emission MJD rounded to a double, which
+// would cost up to 0.3 us * F0 -- and the glitch masks are taken at the emission time.
+template <bool BIN>
+__device__ __forceinline__ double cp_one_t(const CPModel* __restrict__ M, double t, double tau) {
     double te = 0.0;
     if (M->parts & 1) {
         // calcphase.py:80-85: te = sum_{n=1}^{13} coef_n * dt**n, summed in increasing n.
-        const double dt = (t - M->pepoch) * 86400.0;
+        const double dt = BIN ? (t - M->pepoch) * 86400.0 - tau : (t - M->pepoch) * 86400.0;
         double dn = dt;
         const int nt = M->nterms;
         for (int k = 0; k < nt; ++k) {
@@ -408,7 +431,15 @@ __device__ __forceinline__ double cp_one(const CPModel* __restrict__ M, double t
         // calcphase.py:98-124
         for (int j = 0; j < M->n_glitch; ++j) {
             const double* g = M->glitch[j];
-            if (t >= g[0]) {
+            if (BIN) {
+                const double dts = (t - g[0]) * 86400.0 - tau;
+                if (dts >= 0.0) {
+                    const double td = g[6] * 86400.0;
+                    const double ex = (g[6] == 0.0) ? 0.0 : td * (1.0 - exp(-dts / td));
+                    gl += (((g[1] + g[2] * dts) + (0.5 * g[3]) * (dts * dts)) +
+                           ((1.0 / 6.0) * g[4]) * (dts * dts * dts)) + g[5] * ex;
+                }
+            } else if (t >= g[0]) {
                 const double dts = (t - g[0]) * 86400.0;
                 const double ex = (g[6] == 0.0) ? 0.0 : (g[6] * 86400.0) * (1.0 - exp(-(t - g[0]) / g[6]));
                 gl += (((g[1] + g[2] * dts) + (0.5 * g[3]) * (dts * dts)) + ((1.0 / 6.0) * g[4]) * (dts * dts * dts)) +
@@ -419,8 +450,9 @@ __device__ __forceinline__ double cp_one(const CPModel* __restrict__ M, double t
     double wv = 0.0;
     if ((M->parts & 4) && M->n_wave > 0) {
         // calcphase.py:138-149
+        const double dw = BIN ? (t - M->wave_epoch) - tau / 86400.0 : (t - M->wave_epoch);
         for (int j = 1; j <= M->n_wave; ++j) {
-            const double arg = (j * M->wave_om) * (t - M->wave_epoch);
+            const double arg = (j * M->wave_om) * dw;
             wv += (M->wave_ab[j - 1][0] * sin(arg)) + (M->wave_ab[j - 1][1] * cos(arg));
         }
         wv *= M->f0;
@@ -428,19 +460,32 @@ __device__ __forceinline__ double cp_one(const CPModel* __restrict__ M, double t
     return te + gl + wv;
 }
 
+__device__ __forceinline__ double cp_one(const CPModel* __restrict__ M, double t) { return cp_one_t<false>(M, t, 0.0); }
+
+// the phase of a kernel argument: cp_one, or (BIN) cp_one at the emission time of the model's orbit
+template <bool BIN>
+__device__ __forceinline__ double cp_args_one(const CPModel* __restrict__ M, const CPArgs<BIN>& A, double t) {
+    if constexpr (BIN) {
+        return cp_one_t<true>(M, t, bin_delay(&A.b, t));
+    } else {
+        return cp_one_t<false>(M, t, 0.0);
+    }
+}
+
 // Two photons per thread, 16-byte loads and stores (24 B of HBM traffic per photon; non-temporal loads and
 // stores measured the same, profiles/r1_final/ab_cos6_nt.log). One pair per thread over a
 // grid that covers the array (up to 2^28 pairs per sweep): 5.5-5.6 TB/s at 1e8 photons, against 4.6-5.1 TB/s
 // for a 4096-block grid-stride loop with 1, 2 or 4 loads in flight per thread (profiles/r1_s4/calcphase_ab.log).
+template <bool BIN>
 __global__ __launch_bounds__(256) void k_calcphase_vec(const double2* __restrict__ t, int64_t npair,
-                                                       const CPModel Mv, double2* __restrict__ total,
+                                                       const CPArgs<BIN> Mv, double2* __restrict__ total,
                                                        double2* __restrict__ folded, double fscale) {
-    const CPModel* M = &Mv;  // the model rides in the kernel arguments (no upload, no copy to the stack)
+    const CPModel* M = &Mv.m;  // the model rides in the kernel arguments (no upload, no copy to the stack)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npair; i += (int64_t)gridDim.x * blockDim.x) {
         const double2 tv = t[i];
         double2 tot;
-        tot.x = cp_one(M, tv.x);
-        tot.y = cp_one(M, tv.y);
+        tot.x = cp_args_one<BIN>(M, Mv, tv.x);
+        tot.y = cp_args_one<BIN>(M, Mv, tv.y);
         total[i] = tot;
         if (folded) {
             double2 fo;
@@ -451,12 +496,13 @@ __global__ __launch_bounds__(256) void k_calcphase_vec(const double2* __restrict
     }
 }
 
+template <bool BIN>
 __global__ __launch_bounds__(256) void k_calcphase_scalar(const double* __restrict__ t, int64_t n,
-                                                          const CPModel Mv, double* __restrict__ total,
+                                                          const CPArgs<BIN> Mv, double* __restrict__ total,
                                                           double* __restrict__ folded, double fscale) {
-    const CPModel* M = &Mv;
+    const CPModel* M = &Mv.m;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const double tot = cp_one(M, t[i]);
+        const double tot = cp_args_one<BIN>(M, Mv, t[i]);
         total[i] = tot;
         if (folded) folded[i] = (tot - floor(tot)) * fscale;
     }
@@ -1677,6 +1723,57 @@ static void make_cpmodel(const crimp_timing_model* model, int32_t parts, CPModel
     std::memcpy(hm.wave_ab, model->wave_ab, sizeof(hm.wave_ab));
 }
 
+// the limits of a model's binary orbit (include/crimp_hip.h: crimp_binary_delay); none set is fine
+static int check_binary(const crimp_timing_model* m) {
+    if (m->binary == CRIMP_BINARY_NONE) return CRIMP_OK;
+    ARGCHK(m->binary == CRIMP_BINARY_BT || m->binary == CRIMP_BINARY_ELL1,
+           "binary must be CRIMP_BINARY_NONE, CRIMP_BINARY_BT or CRIMP_BINARY_ELL1");
+    const bool bt = m->binary == CRIMP_BINARY_BT;
+    ARGCHK(std::isfinite(m->bin_pb) && std::isfinite(m->bin_pbdot) && std::isfinite(m->bin_a1) &&
+               std::isfinite(m->bin_a1dot) && std::isfinite(m->bin_t0) && std::isfinite(m->bin_ecc) &&
+               std::isfinite(m->bin_om) && std::isfinite(m->bin_omdot) && std::isfinite(m->bin_gamma) &&
+               std::isfinite(m->bin_eps1) && std::isfinite(m->bin_eps2), "a binary parameter is not finite");
+    ARGCHK(m->bin_pb > 0.0, "PB must be positive");
+    ARGCHK(m->bin_a1 >= 0.0, "A1 must be >= 0");
+    double e = m->bin_ecc;
+    if (bt) {
+        ARGCHK(e >= 0.0 && e < 1.0, "ECC must be in [0, 1)");
+    } else {
+        e = std::hypot(m->bin_eps1, m->bin_eps2);
+        ARGCHK(e < 1.0, "EPS1^2 + EPS2^2 must be below 1");
+    }
+    ARGCHK(2.0 * 3.141592653589793 * m->bin_a1 / (m->bin_pb * 86400.0 * (1.0 - e)) < 0.5,
+           "2 pi A1 / (PB (1 - e)) must be below 1/2");
+    return CRIMP_OK;
+}
+
+// the kernels' form of the orbit (angles in radians, PB in seconds)
+static void make_binmodel(const crimp_timing_model* m, BinModel* out) {
+    const bool bt = m->binary == CRIMP_BINARY_BT;
+    const double deg = 3.141592653589793 / 180.0;
+    BinModel& b = *out;
+    b = BinModel{};
+    b.kind = m->binary;
+    b.t0 = m->bin_t0;
+    b.pb = m->bin_pb * 86400.0;
+    b.pbdot = m->bin_pbdot;
+    b.a1dot = m->bin_a1dot;
+    b.a1 = m->bin_a1;
+    b.ecc = bt ? m->bin_ecc : 0.0;
+    b.s1me2 = bt ? std::sqrt((1.0 - m->bin_ecc) * (1.0 + m->bin_ecc)) : 1.0;
+    b.om = bt ? m->bin_om * deg : 0.0;
+    b.omdot = bt ? m->bin_omdot * deg / (365.25 * 86400.0) : 0.0;
+    b.gamma = bt ? m->bin_gamma : 0.0;
+    b.eps1 = bt ? 0.0 : m->bin_eps1;
+    b.eps2 = bt ? 0.0 : m->bin_eps2;
+    b.amp = bt ? 1.0 + m->bin_ecc : 1.0 + 0.5 * (std::fabs(m->bin_eps1) + std::fabs(m->bin_eps2));
+}
+
+// a call evaluates at the emission time: the caller asked for it (parts bit 3) and the model has an orbit
+static bool wants_binary(const crimp_timing_model* m, int32_t parts) {
+    return (parts & CRIMP_PART_EMISSION) && m->binary != CRIMP_BINARY_NONE;
+}
+
 extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timing_model* model, int32_t parts,
                                double* total, double* folded, uint32_t flags, void* stream) {
     ARGCHK(n >= 0, "n < 0");
@@ -1684,12 +1781,19 @@ extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timin
     ARGCHK(model != nullptr && ((total != nullptr && t_mjd != nullptr) || n == 0), "null argument");
     ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
     ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+    if (const int rc = check_binary(model)) return rc;
     if (n == 0) return CRIMP_OK;
     const Call call(flags, stream);
     const bool dev = call.dev;
     hipStream_t s = call.s;
-    CPModel hm{};
-    make_cpmodel(model, parts, &hm);
+    const bool bin = wants_binary(model, parts);
+    CPArgs<false> hm{};
+    make_cpmodel(model, parts, &hm.m);
+    CPArgs<true> hb{};
+    if (bin) {
+        hb.m = hm.m;
+        make_binmodel(model, &hb.b);
+    }
     {
         Scratch sc(s);
         const double* dt = nullptr;
@@ -1705,16 +1809,53 @@ extern "C" int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timin
         // CRIMP_FLAG_FOLD_RADIANS: the folded phase times 2 pi, the host's `folded * (2 * np.pi)` of the Cauchy and
         // von Mises fits (measureToAs.py:195, :200) in the same fp64 multiply
         const double fscale = (flags & CRIMP_FLAG_FOLD_RADIANS) ? 2.0 * 3.141592653589793 : 1.0;
-        if (vec)
-            k_calcphase_vec<<<blocks, 256, 0, s>>>(reinterpret_cast<const double2*>(dt), n / 2, hm,
-                                                     reinterpret_cast<double2*>(dtot), reinterpret_cast<double2*>(dfol),
-                                                     fscale);
+        if (vec && bin)
+            k_calcphase_vec<true><<<blocks, 256, 0, s>>>(reinterpret_cast<const double2*>(dt), n / 2, hb,
+                                                           reinterpret_cast<double2*>(dtot),
+                                                           reinterpret_cast<double2*>(dfol), fscale);
+        else if (vec)
+            k_calcphase_vec<false><<<blocks, 256, 0, s>>>(reinterpret_cast<const double2*>(dt), n / 2, hm,
+                                                            reinterpret_cast<double2*>(dtot),
+                                                            reinterpret_cast<double2*>(dfol), fscale);
+        else if (bin)
+            k_calcphase_scalar<true><<<blocks, 256, 0, s>>>(dt, n, hb, dtot, dfol, fscale);
         else
-            k_calcphase_scalar<<<blocks, 256, 0, s>>>(dt, n, hm, dtot, dfol, fscale);
+            k_calcphase_scalar<false><<<blocks, 256, 0, s>>>(dt, n, hm, dtot, dfol, fscale);
         HIPCHK(hipGetLastError());
         kt.stop();
         HIPCHK(copy_back(s, total, dtot, (size_t)n, dev));
         HIPCHK(copy_back(s, folded, dfol, (size_t)n, dev));
+    }
+    return finish(s, flags);
+}
+
+extern "C" int crimp_binary_delay(const double* t_mjd, int64_t n, const crimp_timing_model* model, double* delay_s,
+                                  double* t_emit_mjd, uint32_t flags, void* stream) {
+    ARGCHK(n >= 0, "n < 0");
+    ARGCHK(model != nullptr && ((delay_s != nullptr && t_mjd != nullptr) || n == 0), "null argument");
+    ARGCHK(model->binary != CRIMP_BINARY_NONE, "the model has no binary");
+    if (const int rc = check_binary(model)) return rc;
+    if (n == 0) return CRIMP_OK;
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    BinModel hb{};
+    make_binmodel(model, &hb);
+    {
+        Scratch sc(s);
+        const double* dt = nullptr;
+        double *dd = nullptr, *de = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, (size_t)n, dev, &dt));
+        HIPCHK(stage_out(sc, delay_s, (size_t)n, dev, &dd));
+        HIPCHK(stage_out(sc, t_emit_mjd, (size_t)n, dev, &de));
+        const int blocks = (int)std::min<int64_t>(cdiv(n, 256), int64_t(1) << 20);
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        k_binary_delay<<<blocks, 256, 0, s>>>(dt, n, hb, dd, de);
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, delay_s, dd, (size_t)n, dev));
+        HIPCHK(copy_back(s, t_emit_mjd, de, (size_t)n, dev));
     }
     return finish(s, flags);
 }
@@ -3114,6 +3255,7 @@ extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_m
     if (model != nullptr) {
         ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
         ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+        if (const int rc = check_binary(model)) return rc;
     }
     CubeDims D{};
     D.ny = ny;
@@ -3148,8 +3290,15 @@ extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_m
     const Call call(flags, stream);
     const bool dev = call.dev;
     hipStream_t s = call.s;
-    CPModel hm{};
-    if (model) make_cpmodel(model, 7, &hm);
+    // a model with an orbit is folded at the emission time (crimp_calcphase's parts 7 | 8)
+    const bool bin = model != nullptr && wants_binary(model, 7 | CRIMP_PART_EMISSION);
+    CPArgs<false> hm{};
+    if (model) make_cpmodel(model, 7, &hm.m);
+    CPArgs<true> hb{};
+    if (bin) {
+        hb.m = hm.m;
+        make_binmodel(model, &hb.b);
+    }
     {
         Scratch sc(s);
         const double *dx = nullptr, *dy = nullptr, *dz = nullptr;
@@ -3180,10 +3329,18 @@ extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_m
             const size_t lds = cube_lds_bytes(D);
             KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
             kt.start();
-            auto kern = vec ? (cube_is_map(D) ? k_phase_cube<true, true> : k_phase_cube<true, false>)
-                            : (cube_is_map(D) ? k_phase_cube<false, true> : k_phase_cube<false, false>);
-            kern<<<blocks, kCubeBlock, lds, s>>>(dx, dy, dz, n, hm, dtab, dzoff, D,
-                                                 reinterpret_cast<unsigned long long*>(dc));
+            if (bin) {
+                auto kern = vec ? (cube_is_map(D) ? k_phase_cube<true, true, true> : k_phase_cube<true, false, true>)
+                                : (cube_is_map(D) ? k_phase_cube<false, true, true> : k_phase_cube<false, false, true>);
+                kern<<<blocks, kCubeBlock, lds, s>>>(dx, dy, dz, n, hb, dtab, dzoff, D,
+                                                     reinterpret_cast<unsigned long long*>(dc));
+            } else {
+                auto kern = vec ? (cube_is_map(D) ? k_phase_cube<true, true, false> : k_phase_cube<true, false, false>)
+                                : (cube_is_map(D) ? k_phase_cube<false, true, false>
+                                                  : k_phase_cube<false, false, false>);
+                kern<<<blocks, kCubeBlock, lds, s>>>(dx, dy, dz, n, hm, dtab, dzoff, D,
+                                                     reinterpret_cast<unsigned long long*>(dc));
+            }
             HIPCHK(hipGetLastError());
             kt.stop();
         }
@@ -3240,6 +3397,7 @@ static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_mo
         ARGCHK(fm.n_glitch >= 0 && fm.n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
         ARGCHK(fm.n_wave >= 0 && fm.n_wave <= CRIMP_MAX_WAVE && wm.n_wave >= 0 && wm.n_wave <= CRIMP_MAX_WAVE,
                "n_wave out of range");
+        ARGCHK(fm.binary == CRIMP_BINARY_NONE && wm.binary == CRIMP_BINARY_NONE, "binary models are not fitted yet");
         ARGCHK(top_gl < fm.n_glitch, "slot names a glitch outside the model");
         ARGCHK(top_wv < fm.n_wave, "slot names a wave harmonic outside the model");
         TFModel& tm = (*models)[(size_t)i];
@@ -3549,6 +3707,7 @@ extern "C" int crimp_sim_events(const crimp_timing_model* model, const crimp_sim
     *n_out = 0;
     ARGCHK(model->n_glitch >= 0 && model->n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
     ARGCHK(model->n_wave >= 0 && model->n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+    if (const int rc = check_binary(model)) return rc;
     ARGCHK(std::isfinite(mjd_start) && std::isfinite(out_offset_s), "mjd_start and out_offset_s must be finite");
     ARGCHK(std::isfinite(span_s) && span_s > 0.0, "span_s must be positive and finite");
     ARGCHK(std::isfinite(cell_s) && cell_s > 0.0, "cell_s must be positive and finite");
@@ -3606,8 +3765,16 @@ extern "C" int crimp_sim_events(const crimp_timing_model* model, const crimp_sim
         }
     }
     if (n_cells == 0) return CRIMP_OK;  // an empty cell range: no events, every argument checked all the same
-    CPModel hm{};
-    make_cpmodel(model, 7, &hm);
+    // with an orbit the rate follows the shape at the phase of the emission time (parts 7 | 8); the Jacobian
+    // 1 - dtau/dt of the rate, below 2 pi x / pb, is ignored
+    const bool bin = wants_binary(model, 7 | CRIMP_PART_EMISSION);
+    CPArgs<false> hm{};
+    make_cpmodel(model, 7, &hm.m);
+    CPArgs<true> hb{};
+    if (bin) {
+        hb.m = hm.m;
+        make_binmodel(model, &hb.b);
+    }
     {
         Scratch sc(s);
         const double *dgti = nullptr, *dsteps = nullptr;
@@ -3621,7 +3788,12 @@ extern "C" int crimp_sim_events(const crimp_timing_model* model, const crimp_sim
         KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
         kt.start();
         HIPCHK(hipMemsetAsync(dcnt + n_cells, 0, sizeof(int64_t), s));
-        k_sim_cells<false><<<(unsigned)n_cells, 64, 0, s>>>(hm, A, dsteps, dgti, dcnt, nullptr, nullptr, nullptr);
+        if (bin)
+            k_sim_cells<false, true><<<(unsigned)n_cells, 64, 0, s>>>(hb, A, dsteps, dgti, dcnt, nullptr, nullptr,
+                                                                      nullptr);
+        else
+            k_sim_cells<false, false><<<(unsigned)n_cells, 64, 0, s>>>(hm, A, dsteps, dgti, dcnt, nullptr, nullptr,
+                                                                       nullptr);
         HIPCHK(hipGetLastError());
         k_sim_tile_sums<<<(unsigned)tiles, kSimScanBlock, 0, s>>>(dcnt, n1, dsums);
         k_sim_scan_top<<<1, kSimScanBlock, 0, s>>>(dsums, tiles);
@@ -3641,7 +3813,10 @@ extern "C" int crimp_sim_events(const crimp_timing_model* model, const crimp_sim
         HIPCHK(stage_out(sc, t_out, (size_t)total, dev, &dt));
         HIPCHK(stage_out(sc, bkg_out, (size_t)total, dev, &db));
         if (total > 0) {
-            k_sim_cells<true><<<(unsigned)n_cells, 64, 0, s>>>(hm, A, dsteps, dgti, nullptr, dcnt, dt, db);
+            if (bin)
+                k_sim_cells<true, true><<<(unsigned)n_cells, 64, 0, s>>>(hb, A, dsteps, dgti, nullptr, dcnt, dt, db);
+            else
+                k_sim_cells<true, false><<<(unsigned)n_cells, 64, 0, s>>>(hm, A, dsteps, dgti, nullptr, dcnt, dt, db);
             HIPCHK(hipGetLastError());
         }
         kt.stop();

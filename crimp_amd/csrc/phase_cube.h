@@ -137,15 +137,18 @@ __device__ __forceinline__ void cube_bins(const double* (&e)[K], const int (&nb)
 // MAP: the shape of a profile or a phase-time map, fixed at compile time -- no z axis, near-uniform y (if any) and
 // phase edges, LDS counting -- so that its loop carries neither the binary searches nor the column and atomic
 // choices (the kernel is bound by its instruction count: 0.444 ms for the fused 32 x 12 map in the general form).
-template <bool VEC, bool MAP>
+// BIN: the model carries a binary orbit and the fused phase is the one at the emission time (crimp_calcphase's
+// parts 7 | 8); BIN = false is the kernel of a build without orbits.
+template <bool VEC, bool MAP, bool BIN>
 __global__ __launch_bounds__(kCubeBlock) void k_phase_cube(const double* __restrict__ x, const double* __restrict__ y,
-                                                           const double* __restrict__ z, int64_t n, const CPModel Mv,
+                                                           const double* __restrict__ z, int64_t n,
+                                                           const CPArgs<BIN> Mv,
                                                            const double* __restrict__ tables,
                                                            const int32_t* __restrict__ zoff_g, const CubeDims D,
                                                            unsigned long long* __restrict__ counts) {
     extern __shared__ double cube_sm[];
     constexpr int K = kCubeK;
-    const CPModel* M = &Mv;
+    const CPModel* M = &Mv.m;
     const int tid = threadIdx.x;
     const bool has_z = MAP ? false : D.has_z != 0, lds = MAP ? true : D.R != 0;
     const bool uni_y = MAP ? true : D.uni_y != 0, uni_p = MAP ? true : D.uni_p != 0;
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(kCubeBlock) void k_phase_cube(const double* __restr
         for (int k = 0; k < K; ++k) {
             ph[k] = xv[k];
             if (D.fused) {
-                const double tot = cp_one(M, xv[k]);
+                const double tot = cp_args_one<BIN>(M, Mv, xv[k]);
                 ph[k] = tot - floor(tot);  // k_calcphase_vec's folded value
             }
         }

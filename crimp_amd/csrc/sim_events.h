@@ -42,7 +42,7 @@ struct SimArgs {
     uint64_t seed;
     int32_t days;
 };
-static_assert(sizeof(CPModel) + sizeof(SimArgs) + 64 <= 4096,
+static_assert(sizeof(CPArgs<true>) + sizeof(SimArgs) + 64 <= 4096,
               "the timing model and the shape ride in the kernel arguments (4 KB limit)");
 
 // mjd inside some [start, stop) of the sorted, disjoint GTIs
@@ -58,8 +58,9 @@ __device__ __forceinline__ bool sim_in_gti(const double* __restrict__ gti, int64
 // One block of 64 threads (one wave) per cell. FILL = false: cnt[cell] = survivors; FILL = true: the same cell again,
 // times to t_out[off[cell] + rank], background flags to bkg_out (may be NULL); off has one entry more than there are
 // cells (the total).
-template <bool FILL>
-__global__ __launch_bounds__(64) void k_sim_cells(const CPModel Mv, const SimArgs A, const double* __restrict__ steps,
+// BIN: the rate follows the template at the phase of the emission time (the orbit stays in the kernel arguments).
+template <bool FILL, bool BIN>
+__global__ __launch_bounds__(64) void k_sim_cells(const CPArgs<BIN> Mv, const SimArgs A, const double* __restrict__ steps,
                                                   const double* __restrict__ gti, int64_t* __restrict__ cnt,
                                                   const int64_t* __restrict__ off, double* __restrict__ t_out,
                                                   uint8_t* __restrict__ bkg_out) {
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(64) void k_sim_cells(const CPModel Mv, const SimArg
     static_assert(sizeof(CPModel) % sizeof(double) == 0, "CPModel is copied to LDS in 8-byte words");
     const int lane = threadIdx.x;
     {
-        const char* src = reinterpret_cast<const char*>(&Mv);
+        const char* src = reinterpret_cast<const char*>(&Mv.m);
         char* dst = reinterpret_cast<char*>(&Ms);
         for (int i = lane; i < (int)(sizeof(CPModel) / sizeof(double)); i += 64)
             __builtin_memcpy(dst + 8 * i, src + 8 * i, 8);
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(64) void k_sim_cells(const CPModel Mv, const SimArg
         if (s < end) {
             const double mjd = A.mjd_start + s / 86400.0;
             if (A.ngti == 0 || sim_in_gti(gti, A.ngti, mjd)) {
-                const double ph = cp_one(M, mjd);
+                const double ph = cp_args_one<BIN>(M, Mv, mjd);
                 const double fr = ph - floor(ph);
                 double S;
                 if (tpl) {

@@ -2,12 +2,18 @@
 (Taylor + glitch terms), with the spin frequency there -- CRIMP v2.3.0
 ``ephemIntegerRotation.py:25-86``. A per-ToA scalar used only by the .tim writer; the
 phase is evaluated on the host with the reference's own NumPy expression
-(calcphase.py:80-126) so the written ToAs match CRIMP's digits."""
+(calcphase.py:80-126) so the written ToAs match CRIMP's digits.
+
+A model with a binary orbit (BINARY BT | ELL1, not in the reference) is evaluated at the emission time: the delay of
+crimp_amd.binarymodels.binary_delay_host enters each epoch difference in seconds. The Newton step keeps
+the spin frequency as its slope; the true slope differs by the factor 1 - dtau/dt, within 2 pi x / pb of 1, so the
+iteration still converges inside ``max_iter``."""
 import argparse
 from math import factorial
 
 import numpy as np
 
+from .binarymodels import binary_delay_host, has_binary
 from .ephemTmjd import ephemTmjd
 from .readtimingmodel import ReadTimingModel
 
@@ -20,7 +26,11 @@ def phase_no_waves(t, timMod):
     """Taylor + glitch phase of one MJD (calcphase.py:73-126 evaluated on a 1-element array)."""
     p = _model(timMod)
     tt = np.atleast_1d(t).astype(float).reshape(-1)
+    # a binary orbit: every epoch difference at the emission time (tau = 0 leaves each expression as it is)
+    tau = binary_delay_host(tt, p) if has_binary(p) else None
     dt = (tt - p["PEPOCH"]) * 86400.0
+    if tau is not None:
+        dt = dt - tau
     te = 0.0
     for nn in range(1, 14):
         te += (1.0 / factorial(nn)) * p["F%d" % (nn - 1)] * (dt ** nn)
@@ -28,13 +38,17 @@ def phase_no_waves(t, timMod):
     ngl = sum(1 for k in p if k.startswith("GLEP_"))
     for jj in range(1, ngl + 1):
         glep = float(p["GLEP_%d" % jj])
-        mask = tt >= glep
+        mask = tt >= glep if tau is None else (tt - glep) * 86400.0 - tau >= 0.0
         if not np.any(mask):
             continue
         g = {b: float(p.get("%s_%d" % (b, jj), 0.0)) for b in ("GLPH", "GLF0", "GLF1", "GLF2", "GLF0D", "GLTD")}
         ta = tt[mask]
         dts = (ta - glep) * 86400.0
-        ex = 0.0 if g["GLTD"] == 0.0 else (g["GLTD"] * 86400.0) * (1.0 - np.exp(-(ta - glep) / g["GLTD"]))
+        days = ta - glep
+        if tau is not None:
+            dts = dts - tau[mask]
+            days = days - tau[mask] / 86400.0
+        ex = 0.0 if g["GLTD"] == 0.0 else (g["GLTD"] * 86400.0) * (1.0 - np.exp(-days / g["GLTD"]))
         gl[mask] += (g["GLPH"] + g["GLF0"] * dts + 0.5 * g["GLF1"] * dts ** 2 + (1.0 / 6.0) * g["GLF2"] * dts ** 3
                      + g["GLF0D"] * ex)
     return float(np.atleast_1d(te + gl)[0])

@@ -13,6 +13,7 @@ import pandas as pd
 from . import ops
 from .calcphase import calcphase
 from .logging_utils import get_logger
+from .binarymodels import require_no_binary
 from .readtimingmodel import (ReadTimingModel, get_parameter_value, patch_miscellaneous, patch_par_values,
                               patch_statistics)
 from .timfile import PulseToAs, readtimfile
@@ -29,7 +30,9 @@ def load_toas_for_fit(tim_file_df: pd.DataFrame, parfile: dict, t_start: float |
     """ToAs of a .tim table as fit input: a DataFrame ['ToA', 'phase', 'phase_err_cycle'], time-sorted, optionally
     cut to [t_start, t_stop]. The phase is calcphase's (on the device) under ``parfile``: minus the pulse number when
     the model has TRACK -2 and the table a ``pn`` column, else folded into [-0.5, 0.5); then mean-subtracted.
-    ``t_mjd_phasewrap`` adds (``mode`` 'add') or removes ('subtract') one cycle from each given MJD on."""
+    ``t_mjd_phasewrap`` adds (``mode`` 'add') or removes ('subtract') one cycle from each given MJD on.
+    ValueError for a model with a binary orbit: the fits do not model it."""
+    require_no_binary(parfile)
     f0 = get_parameter_value(parfile["F0"])
     pt = PulseToAs(tim_file_df)
     pt.time_filter(t_start, t_stop)

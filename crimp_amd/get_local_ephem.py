@@ -14,6 +14,7 @@ from . import ops
 from .ephemIntegerRotation import ephemIntegerRotation
 from .fit_toas import load_toas_for_fit, plot_residuals, prior_box, summarize_chain
 from .logging_utils import configure_logging, get_logger
+from .binarymodels import require_no_binary
 from .readtimingmodel import ReadTimingModel
 from .timfile import readtimfile
 from .utilities_fittoas import DeviceFit, Prior
@@ -31,6 +32,7 @@ def local_ephem_windows(toa_df, parfile, interval_days=90, jump_days=15, t_start
     ``min_interval`` days. Each entry: the window's ToA table ``toas``, ``span_days``, and ``mid`` / ``F0_mid`` /
     ``F1_mid`` -- the integer-rotation epoch nearest before mid-window and the spin parameters of ``parfile`` there."""
     params = ReadTimingModel(parfile).readfulltimingmodel()[0] if isinstance(parfile, str) else parfile
+    require_no_binary(params)  # ValueError: the local fits do not model an orbit
     glitch_epochs = sorted(v for k, v in params.items() if "GLEP_" in k)
     times = toa_df["pulse_ToA"]
     if t_start is None:
@@ -90,6 +92,7 @@ def generate_local_ephemerides(tim_file, parfile, interval_days=90, jump_days=15
                 "t_end %s min_interval %s outputfile %s", tim_file, parfile, interval_days, jump_days, t_start, t_end,
                 min_interval, outputfile)
     params = ReadTimingModel(parfile).readfulltimingmodel()[0]
+    require_no_binary(params)
     glitch_epochs = sorted(v for k, v in params.items() if "GLEP_" in k)
     windows = local_ephem_windows(readtimfile(tim_file), parfile, interval_days, jump_days, t_start, t_end,
                                   min_interval)

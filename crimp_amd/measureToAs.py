@@ -25,7 +25,7 @@ from .logging_utils import configure_logging, get_logger
 from . import ops
 from ._native import FLAG_TIME_DAYS, STAT_H
 from .readPPtemplate import readPPtemplate
-from .readtimingmodel import ReadTimingModel
+from .readtimingmodel import ReadTimingModel, get_parameter_value
 from .timfile import phshiftTotimfile
 from .toafit import ToAFitter, warn_capped
 from .toafit_vary import VaryParamFitter
@@ -216,20 +216,41 @@ def measure_intervals(TIMEMJD, timMod, tempModPP, starts, ends, exposures, phShi
             brutemin=brutemin)
     else:
         res = ToAFitter(folded, offs, E, tmpl, phShiftRes, nbrBins).fit(brutemin=brutemin, vary_amps=bool(varyAmps))
-    freqs = np.atleast_1d(ephemTmjd(mids, tm)["freqAtTmjd"])          # :210
+    freqs = _htest_freqs(mids, tm)                                    # :210
     # :211-212, one trial per interval; TIME_toa * 86400 formed in the kernel (CRIMP_FLAG_TIME_DAYS)
+    ht, hflags = _htest_times(allt, tm)
     if hasattr(allt, "device"):
-        hp = ops.search_sets(allt, torch.as_tensor(offs, device=allt.device),
+        hp = ops.search_sets(ht, torch.as_tensor(offs, device=allt.device),
                              torch.as_tensor(freqs, dtype=torch.float64, device=allt.device), 5, STAT_H,
-                             flags=FLAG_TIME_DAYS).cpu().numpy()
+                             flags=hflags).cpu().numpy()
     else:
-        hp = ops.search_sets(allt, offs, freqs, 5, STAT_H, flags=FLAG_TIME_DAYS)
+        hp = ops.search_sets(ht, offs, freqs, 5, STAT_H, flags=hflags)
     res["ToA_mid"] = mids
     res["htestPow"] = np.asarray(hp)
     return res
 
 
 _HTEST_STREAMS = {}
+
+
+def _htest_times(allt, tm):
+    """(times, search flags) of the per-interval H-test: the photons' MJDs (seconds formed in the kernel), or -- for
+    a model with a binary orbit -- their emission times in seconds since PEPOCH, so that the orbit does not smear the
+    pulse."""
+    from .binarymodels import has_binary
+    if not has_binary(tm):
+        return allt, FLAG_TIME_DAYS
+    tau, _ = ops.binary_delay(allt, tm)
+    return (allt - float(get_parameter_value(tm["PEPOCH"]))) * 86400.0 - tau, 0
+
+
+def _htest_freqs(mids, tm):
+    """The spin frequency of every interval's H-test (measureToAs.py:210): the model's at ToA_mid, for a binary model
+    at the emission time of ToA_mid (ToA_mid itself stays an arrival time)."""
+    from .binarymodels import binary_delay_host, has_binary
+    if has_binary(tm):
+        mids = np.asarray(mids, dtype=np.float64) - binary_delay_host(mids, tm) / 86400.0
+    return np.atleast_1d(ephemTmjd(mids, tm)["freqAtTmjd"])
 
 
 def _folded(allt, tm, model):
@@ -251,7 +272,8 @@ def _fit_block(allt, offs, mids, tm, tmpl, model, E, phShiftRes, nbrBins, varyAm
     import torch
     from ._native import FLAG_ASYNC
     dev = allt.device
-    freqs = np.atleast_1d(ephemTmjd(mids, tm)["freqAtTmjd"])          # :210
+    freqs = _htest_freqs(mids, tm)                                    # :210
+    ht, hflags = _htest_times(allt, tm)
     offs_d = torch.as_tensor(offs, device=dev)
     freqs_d = torch.as_tensor(freqs, dtype=torch.float64, device=dev)
     side = _HTEST_STREAMS.get(dev.index)
@@ -260,8 +282,8 @@ def _fit_block(allt, offs, mids, tm, tmpl, model, E, phShiftRes, nbrBins, varyAm
     cur = torch.cuda.current_stream(dev)
     side.wait_stream(cur)
     with torch.cuda.stream(side):  # :211-212, one trial per interval, TIME_toa * 86400 in the kernel
-        hp_d = ops.search_sets(allt, offs_d, freqs_d, 5, STAT_H, flags=FLAG_ASYNC | FLAG_TIME_DAYS)
-    for t_ in (allt, offs_d, freqs_d, hp_d):
+        hp_d = ops.search_sets(ht, offs_d, freqs_d, 5, STAT_H, flags=FLAG_ASYNC | hflags)
+    for t_ in (allt, ht, offs_d, freqs_d, hp_d):
         t_.record_stream(side)
     folded = _folded(allt, tm, model)
     res = ToAFitter(folded, offs, E, tmpl, phShiftRes, nbrBins).fit(brutemin=brutemin, vary_amps=bool(varyAmps))

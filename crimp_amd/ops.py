@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from . import _native as N
+from . import binarymodels
 
 
 def _modeltm(tm):
@@ -42,6 +43,8 @@ def _modeltm(tm):
         for j in range(1, nharm + 1):
             m.wave_ab[j - 1][0] = float(d["WAVE%d" % j]["A"])
             m.wave_ab[j - 1][1] = float(d["WAVE%d" % j]["B"])
+    if "BINARY" in d:  # the orbit (ValueError outside its limits); without it the tail stays zero: no binary
+        binarymodels.fill_native(m, d)
     return m
 
 
@@ -57,9 +60,29 @@ def calcphase(t_mjd, timing_model_dict, parts=7, total=None, folded=None, want_f
     op = b.arg(total, np.float64, writable=True)
     fp = b.arg(folded, np.float64, writable=True) if folded is not None else None
     m = _modeltm(timing_model_dict)
+    if m.binary:  # a model with an orbit: the requested parts at the emission time
+        parts = int(parts) | N.PART_EMISSION
     with b.device_guard():
         N.check(L.crimp_calcphase(tp, n, ctypes.byref(m), int(parts), op, fp, b.flags(flags), b.stream()))
     return total, folded
+
+
+def binary_delay(t_mjd, timing_model_dict, delay=None, t_emit=None, want_emit=False, flags=0):
+    """(tau in seconds, emission MJD or None) of crimp_binary_delay for a flat array of arrival times (MJD)."""
+    L = N.load()
+    b = N.Buffers()
+    tp = b.arg(t_mjd, np.float64)
+    n = int(t_mjd.numel() if N._is_torch(t_mjd) else np.size(t_mjd))
+    if delay is None:
+        delay = _empty_like_input(t_mjd, n, b)
+    if t_emit is None and want_emit:
+        t_emit = _empty_like_input(t_mjd, n, b)
+    dp = b.arg(delay, np.float64, writable=True)
+    ep = b.arg(t_emit, np.float64, writable=True) if t_emit is not None else None
+    m = timing_model_dict if isinstance(timing_model_dict, N.TimingModel) else _modeltm(timing_model_dict)
+    with b.device_guard():
+        N.check(L.crimp_binary_delay(tp, n, ctypes.byref(m), dp, ep, b.flags(flags), b.stream()))
+    return delay, t_emit
 
 
 def _empty_like_input(a, n, b, dtype=np.float64):
@@ -437,6 +460,8 @@ def _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases):
     nprob = len(fit_bases)
     if len(wave_bases) != nprob:
         raise ValueError("one fit base and one wave base per problem")
+    if any(m.binary for m in fit_bases) or any(m.binary for m in wave_bases):
+        raise ValueError("binary models are not fitted yet")
     if offsets is None:
         n = int(t.numel() if N._is_torch(t) else np.size(t))
         offsets = np.array([0, n], dtype=np.int64)

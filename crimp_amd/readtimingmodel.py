@@ -7,12 +7,23 @@ Restates the behaviour of CRIMP's ``readtimingmodel.py`` (v2.3.0):
   * WAVEEPOCH, WAVE_OM (+flag) and WAVEj A/B pairs                (:152-209)
   * readfulltimingmodel() -> (values, flags, both), adding TRACK=-2 when present (:212-233, :324-335)
   * a value token goes through complex(tok).real, a flag is 0/1 or 0 (:38-53)
+
+Beyond the reference: readbinary() reads the orbit of a ``BINARY BT`` / ``BINARY ELL1`` model, and
+readfulltimingmodel() merges it in. A .par without a BINARY line reads exactly as before.
 """
+import logging
 import re
 
 import numpy as np
 
 _TAYLOR = ["PEPOCH"] + ["F%d" % i for i in range(13)]
+BINARY_MODELS = ("BT", "ELL1")
+# key -> aliases; every key defaults to 0 when the model has a BINARY line
+_BINARY = {"PB": (), "PBDOT": (), "A1": (), "A1DOT": ("XDOT",), "T0": (), "ECC": ("E",), "OM": (), "OMDOT": (),
+           "GAMMA": (), "TASC": (), "EPS1": (), "EPS2": ()}
+_BINARY_ALIAS = {a: k for k, al in _BINARY.items() for a in al}
+_BINARY_IGNORED = ("SINI", "M2", "EDOT", "EPS1DOT", "EPS2DOT")
+logger = logging.getLogger(__name__)
 _GLITCH = (("GLEP_", 0.0), ("GLPH_", 0.0), ("GLF0_", 0.0), ("GLF1_", 0.0), ("GLF2_", 0.0), ("GLF0D_", 0.0),
            ("GLTD_", 1.0))
 
@@ -105,13 +116,51 @@ class ReadTimingModel:
                     break
         return vals, flags, both
 
+    def readbinary(self):
+        """The orbit of a ``BINARY BT`` or ``BINARY ELL1`` model as (values, flags, both); all three empty without a
+        BINARY line. ``BINARY`` is the model's name in upper case; PB, PBDOT, A1, A1DOT (or XDOT), T0, ECC (or E),
+        OM, OMDOT, GAMMA, TASC, EPS1, EPS2 are the .par's numbers as written (0 when absent; the 1e-12 unit
+        convention of PBDOT and A1DOT is applied where the orbit is evaluated, crimp_amd.binarymodels). Another
+        BINARY value is a ValueError; SINI, M2, EDOT, EPS1DOT, EPS2DOT are ignored with one warning (no Shapiro
+        delay, no eccentricity derivatives)."""
+        lines = [ln.split() for ln in self._lines()]
+        name = None
+        for tok in lines:
+            if len(tok) >= 2 and tok[0].upper() == "BINARY":
+                name = tok[1].upper()
+        if name is None:
+            return {}, {}, {}
+        if name not in BINARY_MODELS:
+            raise ValueError("BINARY %s is not supported: the supported binary models are BT and ELL1" % name)
+        vals = {"BINARY": name}
+        flags = {"BINARY": 0}
+        both = {"BINARY": {"value": name, "flag": None}}
+        for k in _BINARY:
+            vals[k], flags[k], both[k] = np.float64(0), 0, {"value": np.float64(0), "flag": 0}
+        ignored = []
+        for tok in lines:
+            if len(tok) < 2:
+                continue
+            key = _BINARY_ALIAS.get(tok[0], tok[0])
+            if key in _BINARY:
+                v, f = _value_flag(tok[1:])
+                vals[key], flags[key] = v, f
+                both[key] = {"value": v, "flag": f}
+            elif tok[0] in _BINARY_IGNORED:
+                ignored.append(tok[0])
+        if ignored:
+            logger.warning("binary model %s: %s ignored (no Shapiro delay, no eccentricity derivatives)", name,
+                           ", ".join(ignored))
+        return vals, flags, both
+
     def readfulltimingmodel(self):
         te = self.readtaylorexpansion()
         gl = self.readglitches()
         wv = self.readwaves()
-        vals = {**te[0], **gl[0], **wv[0]}
-        flags = {**te[1], **gl[1], **wv[1]}
-        both = {**te[2], **gl[2], **wv[2]}
+        bn = self.readbinary()
+        vals = {**te[0], **gl[0], **wv[0], **bn[0]}
+        flags = {**te[1], **gl[1], **wv[1], **bn[1]}
+        both = {**te[2], **gl[2], **wv[2], **bn[2]}
         if self.readmiscellaneous().get("TRACK") == -2:
             vals["TRACK"] = -2.0
             both["TRACK"] = {"value": -2.0, "flag": 0}
@@ -203,7 +252,7 @@ def patch_par_values(in_path: str, out_path: str, *, new_values: dict, float_fmt
             continue
         key, gap, _, flag_gap, flag, old_unc, tail = m.groups()
         v = plain(new_values.get(key))
-        if v is None or isinstance(v, dict):
+        if v is None or isinstance(v, (dict, str)):  # (a model's BINARY name is not a number: its line stays)
             out.append(line)
             continue
         text = key + gap + format(float(v), float_fmt)

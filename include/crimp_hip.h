@@ -78,6 +78,11 @@ extern "C" {
 #define CRIMP_MAX_WAVE 64
 #define CRIMP_MAX_COMP 16
 
+#define CRIMP_BINARY_NONE 0
+#define CRIMP_BINARY_BT 1    /* Blandford & Teukolsky 1976 */
+#define CRIMP_BINARY_ELL1 2  /* Lange et al. 2001 */
+#define CRIMP_PART_EMISSION 8 /* crimp_calcphase parts bit 3: the requested parts at the emission time of a binary model */
+
 /* Values of a .par timing model as calcphase consumes them
  * (readtimingmodel.py:212-233; calcphase.py:73-149). */
 typedef struct crimp_timing_model {
@@ -88,6 +93,15 @@ typedef struct crimp_timing_model {
     int32_t n_wave;                         /* WAVE harmonics used = (#WAVE* keys) - 2 (calcphase.py:142) */
     double wave_epoch, wave_om;             /* WAVEEPOCH (MJD), WAVE_OM (rad/day) */
     double wave_ab[CRIMP_MAX_WAVE][2];      /* WAVEj A, B */
+    /* The binary orbit (not in the reference). A zero-filled tail is "no binary". Angles as in the .par. */
+    int32_t binary;                         /* CRIMP_BINARY_NONE | _BT | _ELL1 */
+    double bin_pb;                          /* PB (days) */
+    double bin_pbdot, bin_a1dot;            /* PBDOT, A1DOT|XDOT, dimensionless (the 1e-12 unit convention applied) */
+    double bin_a1;                          /* A1 (light-seconds) */
+    double bin_t0;                          /* T0 (BT) or TASC (ELL1), MJD */
+    double bin_ecc, bin_om, bin_omdot;      /* BT: ECC, OM (deg), OMDOT (deg/yr of 365.25 d) */
+    double bin_gamma;                       /* BT: GAMMA (s) */
+    double bin_eps1, bin_eps2;              /* ELL1: EPS1, EPS2 */
 } crimp_timing_model;
 
 /* A pulse-profile template (readPPtemplate.py:15-166) with its fixed shape. */
@@ -149,9 +163,24 @@ int crimp_device_count(int32_t* count);
  * parts: bit0 Taylor expansion (:73-85), bit1 glitches (:87-126), bit2 waves (:128-149);
  * 7 = calcphase(). folded may be NULL. n == 0 succeeds without touching anything, and t_mjd and total may then be
  * NULL as well (the data pointer of an empty array). A NaN time gives NaN in total and folded whenever bit0 is set,
- * with every F term zero too (the reference's 0 * NaN). */
+ * with every F term zero too (the reference's 0 * NaN).
+ * parts bit 3 (CRIMP_PART_EMISSION): with a model whose ``binary`` is set, every requested part is evaluated at the
+ * emission time t - tau / 86400, tau the orbital delay of crimp_binary_delay, which enters each part in seconds after
+ * the epoch difference; the glitch masks are taken at the emission time. Without the bit, or without a
+ * binary, the call is the one above, bit for bit. A model with a binary outside the limits of crimp_binary_delay is
+ * CRIMP_ERR_ARG whatever the parts. */
 int crimp_calcphase(const double* t_mjd, int64_t n, const crimp_timing_model* model, int32_t parts,
                     double* total, double* folded, uint32_t flags, void* stream);
+
+/* The orbital (Roemer) delay of a binary model, not in the reference: delay_s[i] = tau, the root of
+ * tau = D(t - tau / 86400), D the BT or ELL1 delay of the emission time; t_emit_mjd (may be NULL) =
+ * t - tau / 86400 rounded once. The orbit and the light-travel equation are solved together by a bracketed Newton
+ * iteration with a compile-time cap; a lane that reaches the cap gives NaN, and so does a NaN time. n == 0 touches
+ * nothing. CRIMP_ERR_ARG, each with its own text and nothing written: binary not _BT / _ELL1, PB <= 0, A1 < 0, ECC
+ * outside [0, 1) (ELL1: EPS1^2 + EPS2^2 >= 1), 2 pi A1 / (PB 86400 (1 - e)) >= 1/2 (beyond it the equation need not
+ * have one root), a non-finite value. */
+int crimp_binary_delay(const double* t_mjd, int64_t n, const crimp_timing_model* model, double* delay_s,
+                       double* t_emit_mjd, uint32_t flags, void* stream);
 
 /* PeriodSearch(time, freq, nbrHarm).ztest()/.htest()/.twod_ztest(freq_dot)
  *   [periodsearch.py:40-125]
