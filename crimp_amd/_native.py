@@ -99,7 +99,8 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_device_count", "crimp_calcphase", "crimp_search", "crimp_search_best", "crimp_best", "crimp_search_sets", "crimp_toa_points",
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
-           "crimp_gather_ranges", "crimp_sim_events", "crimp_binary_delay")
+           "crimp_gather_ranges", "crimp_sim_events", "crimp_binary_delay", "crimp_photon_tile", "crimp_photon_nll",
+           "crimp_photon_mcmc")
 
 _lib = None
 _lock = threading.Lock()
@@ -145,6 +146,11 @@ def load(require_device=True):
             L.crimp_timing_nll.argtypes = [P, P, P, P, i64, MP, MP, FP, P, i64, P, P, u32, P]
             L.crimp_timing_mcmc.argtypes = [P, P, P, P, i64, MP, MP, FP, P, P, P, i32, i64, ctypes.c_uint64, i64, P, P, P,
                                             u32, P]
+            TP = ctypes.POINTER(Template)
+            L.crimp_photon_tile.argtypes = []
+            L.crimp_photon_nll.argtypes = [P, P, i64, MP, FP, TP, ctypes.c_double, i32, P, i64, P, P, u32, P]
+            L.crimp_photon_mcmc.argtypes = [P, P, i64, MP, FP, TP, ctypes.c_double, i32, P, P, P, i32, i64,
+                                            ctypes.c_uint64, P, P, P, u32, P]
             L.crimp_is_sorted.argtypes = [P, i64, ctypes.POINTER(i32), u32, P]
             L.crimp_select_intervals.argtypes = [P, i64, P, P, i64, P, P, P, u32, P]
             L.crimp_gather_ranges.argtypes = [P, i64, P, P, i64, P, u32, P]
@@ -195,6 +201,11 @@ def last_nufft_cells():
     b, r = ctypes.c_int64(0), ctypes.c_int64(0)
     L.crimp_last_nufft_cells(ctypes.byref(b), ctypes.byref(r))
     return int(b.value), int(r.value)
+
+
+def photon_tile():
+    """Photons per tile of the photon-domain likelihood's fixed summation order (crimp_photon_tile)."""
+    return int(load(require_device=False).crimp_photon_tile())
 
 
 NUFFT_CLASSES = ("cellstart", "spread", "merge", "pass1", "pass2", "combine", "finalize")

@@ -1650,6 +1650,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "phase_cube.h"
 #include "timing_fit.h"
 #include "sim_events.h"
+#include "photon_fit.h"
 
 // ============================================================== 6. C-ABI
 // A second stream per device for crimp_toa_fit's overlapped halves (created once, kept for the process)
@@ -3537,6 +3538,163 @@ extern "C" int crimp_timing_mcmc(const double* t_mjd, const double* y, const dou
         HIPCHK(copy_back(s, chain, dchain, rows * nd, dev));
         HIPCHK(copy_back(s, logprob, dlp, rows, dev));
         HIPCHK(copy_back(s, accepted, dacc, (size_t)nprob * w, dev));
+    }
+    return finish(s, flags);
+}
+
+// ---- photon-domain timing fits (photon_fit.h)
+// What both calls hold after their one prologue: the plan's launch shape, the photon fit model, its map and the template
+struct PFCall {
+    PFLaunch L;
+    CPModel base;
+    PFMap map;
+    TplDev T;
+};
+
+// every check of crimp_photon_nll / _mcmc that does not need the device, and the host plan (photon_fit_plan.h)
+static int pf_prologue(int64_t n, const crimp_timing_model* par, const crimp_fit_map* map, const crimp_template* tpl,
+                       double norm, int32_t phoff, int64_t P, PFCall* c) {
+    crimp_timing_model fit;
+    int32_t parts = 0, nterms = 1;
+    if (const char* e = plan_photon_model(par, map, phoff, &fit, &c->map, &parts, &nterms))
+        return set_err(CRIMP_ERR_ARG, e);
+    if (const int rc = make_tpl(tpl, &c->T)) return rc;
+    ARGCHK(std::isfinite(norm) && norm > 0.0, "norm must be positive");
+    if (const char* e = plan_photon_launch(n, P, &c->L)) return set_err(CRIMP_ERR_ARG, e);
+    make_cpmodel(&fit, parts, &c->base);
+    c->base.nterms = nterms;
+    c->base.f0 = 1.0;  // the wave coefficients carry F0 (photon_wave_coef)
+    return CRIMP_OK;
+}
+
+// the device copies every launch of a call reads
+struct PFDev {
+    CPModel* base = nullptr;
+    PFMap* map = nullptr;
+    TplDev* T = nullptr;
+    double2* tab = nullptr;
+    double *psum = nullptr, *pmin = nullptr;
+};
+static int pf_upload(Scratch& sc, hipStream_t s, const PFCall& c, PFDev* d) {
+    HIPCHK(sc.alloc(&d->base, 1));
+    HIPCHK(sc.alloc(&d->map, 1));
+    HIPCHK(sc.alloc(&d->T, 1));
+    HIPCHK(sc.alloc(&d->tab, (size_t)kSinTab));
+    HIPCHK(sc.alloc(&d->psum, (size_t)c.L.partials));
+    HIPCHK(sc.alloc(&d->pmin, (size_t)c.L.partials));
+    HIPCHK(h2d(d->base, &c.base, sizeof(CPModel)));
+    HIPCHK(h2d(d->map, &c.map, sizeof(PFMap)));
+    HIPCHK(h2d(d->T, &c.T, sizeof(TplDev)));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_photon_nll), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)sizeof(PFLds)));
+    k_photon_table<<<kSinTab / 256, 256, 0, s>>>(d->tab);
+    HIPCHK(hipGetLastError());
+    return CRIMP_OK;
+}
+
+extern "C" int crimp_photon_tile(void) { return kPfTile; }
+
+extern "C" int crimp_photon_nll(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                                const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                                const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags,
+                                void* stream) {
+    ARGCHK(t_mjd != nullptr && x != nullptr && pvec != nullptr && nll != nullptr, "null argument");
+    PFCall c;
+    if (const int rc = pf_prologue(n, par, map, tpl, norm, phoff, P, &c)) return rc;
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    const size_t D = (size_t)(c.map.ndim + c.map.phoff);
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dx = nullptr, *dp = nullptr;
+        double *dnll = nullptr, *ddel = nullptr;
+        PFDev d;
+        HIPCHK(stage_in(sc, t_mjd, (size_t)n, dev, &dt));
+        HIPCHK(stage_in(sc, x, (size_t)n, dev, &dx));
+        HIPCHK(stage_in(sc, pvec, (size_t)P * D, dev, &dp));
+        HIPCHK(stage_out(sc, nll, (size_t)P, dev, &dnll));
+        HIPCHK(stage_out(sc, delta, (size_t)P * (size_t)n, dev, &ddel));
+        if (const int rc = pf_upload(sc, s, c, &d)) return rc;
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        k_photon_nll<<<dim3((unsigned)c.L.tiles, (unsigned)c.L.groups), kPfWaves * 64, sizeof(PFLds), s>>>(
+            dt, dx, n, d.base, d.map, d.T, d.tab, norm, dp, nullptr, P, d.psum, d.pmin, ddel);
+        HIPCHK(hipGetLastError());
+        k_photon_reduce<<<(unsigned)cdiv(P, 4), 256, 0, s>>>(d.psum, d.pmin, c.L.tiles, n, norm, P, dnll);
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, nll, dnll, (size_t)P, dev));
+        HIPCHK(copy_back(s, delta, ddel, (size_t)P * (size_t)n, dev));
+    }
+    return finish(s, flags);
+}
+
+extern "C" int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                                 const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                                 const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps,
+                                 uint64_t seed, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
+                                 void* stream) {
+    ARGCHK(t_mjd != nullptr && x != nullptr && p0 != nullptr && lo != nullptr && hi != nullptr && chain != nullptr &&
+               logprob != nullptr && accepted != nullptr, "null argument");
+    PFCall c;
+    if (const int rc = pf_prologue(n, par, map, tpl, norm, phoff, W >= 1 ? W : 1, &c)) return rc;
+    const int32_t D = c.map.ndim + c.map.phoff;
+    ARGCHK(W >= 2 && W % 2 == 0 && W <= 256 && W >= 2 * D, "walkers: even, >= 2 ndim and <= 256");
+    ARGCHK(steps >= 1 && steps <= (int64_t(1) << 31), "steps out of range");
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    const size_t w = (size_t)W, nd = (size_t)D, rows = (size_t)steps * w;
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dx = nullptr;
+        PFDev d;
+        PFMc A{};
+        HIPCHK(stage_in(sc, t_mjd, (size_t)n, dev, &dt));
+        HIPCHK(stage_in(sc, x, (size_t)n, dev, &dx));
+        HIPCHK(stage_in(sc, p0, w * nd, dev, &A.p0));
+        HIPCHK(stage_in(sc, lo, nd, dev, &A.lo));
+        HIPCHK(stage_in(sc, hi, nd, dev, &A.hi));
+        HIPCHK(stage_out(sc, chain, rows * nd, dev, &A.chain));
+        HIPCHK(stage_out(sc, logprob, rows, dev, &A.logprob));
+        HIPCHK(stage_out(sc, accepted, w, dev, &A.accepted));
+        if (const int rc = pf_upload(sc, s, c, &d)) return rc;
+        HIPCHK(sc.alloc(&A.pos, w * nd));
+        HIPCHK(sc.alloc(&A.lp, w));
+        HIPCHK(sc.alloc(&A.nacc, w));
+        HIPCHK(sc.alloc(&A.prop, w * nd));
+        HIPCHK(sc.alloc(&A.pz, w));
+        HIPCHK(sc.alloc(&A.act, w));
+        A.psum = d.psum;
+        A.pmin = d.pmin;
+        A.tiles = c.L.tiles;
+        A.n = n;
+        A.norm = norm;
+        A.W = W;
+        A.D = D;
+        A.seed = seed;
+        const unsigned tiles = (unsigned)c.L.tiles;
+        const int64_t half = W / 2;
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        // the whole chain is queued here; the host waits once, in finish()
+        k_photon_step<<<1, kPfStepWaves * 64, 0, s>>>(A, 0, 0, 0, 0);
+        k_photon_nll<<<dim3(tiles, (unsigned)cdiv(W, kPfWaves)), kPfWaves * 64, sizeof(PFLds), s>>>(
+            dt, dx, n, d.base, d.map, d.T, d.tab, norm, A.pos, A.act, W, d.psum, d.pmin, nullptr);
+        k_photon_step<<<1, kPfStepWaves * 64, 0, s>>>(A, 1, 0, 0, 0);
+        HIPCHK(hipGetLastError());
+        for (int64_t st = 0; st < steps; ++st)
+            for (int h = 0; h < 2; ++h) {
+                k_photon_nll<<<dim3(tiles, (unsigned)cdiv(half, kPfWaves)), kPfWaves * 64, sizeof(PFLds), s>>>(
+                    dt, dx, n, d.base, d.map, d.T, d.tab, norm, A.prop, A.act, half, d.psum, d.pmin, nullptr);
+                k_photon_step<<<1, kPfStepWaves * 64, 0, s>>>(A, 2, st, h, st + 1 == steps && h == 1);
+            }
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, chain, A.chain, rows * nd, dev));
+        HIPCHK(copy_back(s, logprob, A.logprob, rows, dev));
+        HIPCHK(copy_back(s, accepted, A.accepted, w, dev));
     }
     return finish(s, flags);
 }

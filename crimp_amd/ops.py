@@ -533,6 +533,69 @@ def timing_mcmc(t, y, yerr, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed
     return chain.reshape(nprob, steps, W, nd), logprob.reshape(nprob, steps, W), accepted.reshape(nprob, W)
 
 
+def _photon_args(b, t, x, par, phoff):
+    n = int(t.numel() if N._is_torch(t) else np.size(t))
+    if int(x.numel() if N._is_torch(x) else np.size(x)) != n:
+        raise ValueError("t and x differ in length")
+    m = par if isinstance(par, N.TimingModel) else _modeltm(par)
+    if m.binary:
+        raise ValueError("binary models are not fitted yet")
+    return b.arg(t, np.float64), b.arg(x, np.float64), n, m, 1 if phoff else 0
+
+
+def photon_nll(t, x, par, fmap, tpl, norm, pvec, phoff=False, want_delta=False, flags=0):
+    """Unbinned template NLL of the photons folded with ``par`` corrected by each of P vectors (crimp_photon_nll).
+    ``t``: photon MJDs; ``x``: their folded phases under ``par`` (cycles); ``par``: a timing-model dict or
+    N.TimingModel; ``fmap``: ``fit_map`` of the free keys; ``pvec`` [P, D], D = ndim + 1 with ``phoff`` (PHOFF last).
+    Returns nll [P], or (nll, delta [P, n]) with ``want_delta``."""
+    L = N.load()
+    b = N.Buffers()
+    tp, xp, n, m, ph = _photon_args(b, t, x, par, phoff)
+    D = int(fmap.ndim) + ph
+    tot = int(pvec.numel() if N._is_torch(pvec) else np.size(pvec))
+    if tot == 0 or tot % D:
+        raise ValueError("pvec must be [P, %d]" % D)
+    P = tot // D
+    pp = b.arg(pvec, np.float64)
+    nll = _empty_like_input(t, P, b)
+    delta = _empty_like_input(t, P * n, b) if want_delta else None
+    nllp = b.arg(nll, np.float64, writable=True)
+    dp = b.arg(delta, np.float64, writable=True) if want_delta else None
+    with b.device_guard():
+        N.check(L.crimp_photon_nll(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph,
+                                   pp, P, nllp, dp, b.flags(flags), b.stream()))
+    return (nll, delta.reshape(P, n)) if want_delta else nll
+
+
+def photon_mcmc(t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff=False, flags=0):
+    """The ensemble sampler of the photon likelihood (crimp_photon_mcmc): ``p0`` [W, D], ``lo`` / ``hi`` [D] (+-inf: no
+    bound). Returns (chain [steps, W, D], logprob [steps, W], accepted [W]); placement follows ``t``."""
+    L = N.load()
+    b = N.Buffers()
+    tp, xp, n, m, ph = _photon_args(b, t, x, par, phoff)
+    D = int(fmap.ndim) + ph
+    shape = tuple(p0.shape)
+    if len(shape) != 2 or shape[1] != D:
+        raise ValueError("p0 must be [W, %d]" % D)
+    W, steps = int(shape[0]), int(steps)
+    for a in (lo, hi):
+        if int(a.numel() if N._is_torch(a) else np.size(a)) != D:
+            raise ValueError("lo and hi must be [%d]" % D)
+    pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
+    rows = max(steps, 0) * W
+    chain = _empty_like_input(t, rows * D, b)
+    logprob = _empty_like_input(t, rows, b)
+    accepted = _empty_like_input(t, W, b, dtype=np.int64)
+    cp = b.arg(chain, np.float64, writable=True)
+    lpp = b.arg(logprob, np.float64, writable=True)
+    ap = b.arg(accepted, np.int64, writable=True)
+    with b.device_guard():
+        N.check(L.crimp_photon_mcmc(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph,
+                                    pp, lop, hip_, W, steps, int(seed) & 0xFFFFFFFFFFFFFFFF, cp, lpp, ap,
+                                    b.flags(flags), b.stream()))
+    return chain.reshape(steps, W, D), logprob.reshape(steps, W), accepted
+
+
 def is_sorted(t):
     """True when the times are non-decreasing (crimp_is_sorted; a NaN counts as out of order), as
     np.all(t[1:] >= t[:-1])."""

@@ -374,6 +374,43 @@ int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, 
                       int64_t steps, uint64_t seed, int64_t first_problem, double* chain, double* logprob,
                       int64_t* accepted, uint32_t flags, void* stream);
 
+/* Photon-domain timing fits (not in the reference; csrc/photon_fit.h).
+ *
+ * The vector p corrects the model as inject_free_params does, full(p) = par - p on every free key, and its likelihood
+ * is the unbinned template likelihood of the photons folded with full(p):
+ *   delta_i = Phi(t_i; par) - Phi(t_i; full(p))   (cycles; evaluated as one small phase, never as a difference)
+ *   u_i     = x_i - delta_i - PHOFF               (x_i: the folded phase of t_i under par, cycles for every template)
+ *   NLL(p)  = -sum_i ln(m(u_i) / norm), m = norm + the template part (templatemodels.py:64-82, :166-185, :271-290);
+ *             +inf when some m(u_i) <= 0.
+ * par is the full model (one problem per call); map->slot names the free keys (map->branch and map->f0_param are not
+ * read). Admitted slots are the ones in which the phase is linear: CRIMP_FIT_SLOT_F, CRIMP_FIT_SLOT_GLITCH with sub
+ * 1..5 (GLPH, GLF0, GLF1, GLF2, GLF0D) and CRIMP_FIT_SLOT_WAVE. phoff = 1 appends a free phase offset PHOFF (cycles)
+ * as the last entry of every vector: D = ndim + phoff entries. norm (> 0) and tpl->amp_shift are fixed. par, map and
+ * tpl are host pointers always; the arrays follow CRIMP_FLAG_DEVICE_PTRS. CRIMP_FLAG_TIME_KERNELS times the kernels
+ * of a call together (crimp_last_kernel_ms).
+ * CRIMP_ERR_ARG of both calls, nothing written: "n < 1"; a slot outside the model ("slot names ..."); a refused slot
+ * ("GLEP is not fitted to photons", "GLTD is not fitted to photons"); "ndim must be 1..CRIMP_FIT_MAX_DIM - phoff";
+ * "binary models are not fitted yet"; a bad template (crimp_toa_points' texts); "norm must be positive". */
+
+/* Photons per tile of the kernels' fixed summation order (a compile-time constant of the library). */
+int crimp_photon_tile(void);
+
+/* NLL of P vectors over n photons in one launch: pvec[P][D], nll[P], delta (may be NULL) [P][n] = delta_i of every
+ * vector. A value depends on the photons, its vector and crimp_photon_tile() alone: not on P or the launch shape. */
+int crimp_photon_nll(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                     const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                     const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags, void* stream);
+
+/* The ensemble sampler of crimp_timing_mcmc (same move, halves, box prior, rejections and Philox counters, problem
+ * index 0) on log-probability = box prior - the NLL above; logprob equals -crimp_photon_nll(chain) bit for bit. The
+ * walkers live on the device and the whole chain is queued at once: per half-step one likelihood launch for that
+ * half's proposals and one small accept/update launch. p0[W][D]; lo, hi [D]; W even, 2 D <= W <= 256; steps >= 1.
+ * chain[steps][W][D], logprob[steps][W], accepted[W]. */
+int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                      const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                      const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                      double* chain, double* logprob, int64_t* accepted, uint32_t flags, void* stream);
+
 /* Interval selection of measureToAs (measureToAs.py:168-182): TIME[(TIME >= start) & (TIME <= end)] per ToA interval
  * (:173-174) and its first / last photon (ToA_mid, :182).
  * crimp_is_sorted: *unsorted = 1 if some t[i+1] < t[i] (or a NaN), else 0 (host int; t host or device per flags).
