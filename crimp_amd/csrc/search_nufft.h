@@ -1112,17 +1112,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
 // are read once and never written back; the trials' (C_k, S_k) go to CS[t], t the trial's index in the batch.
 // X[beta][pos], beta = p * nrow + r, pos = k1 n2 + k2 holds J = k1 + n1 k2 (ln1 = 0: natural order), J = jc mod n.
 constexpr int kNuFusedPer = kNuTile / 256;  // positions per thread
+// The row k1 of block b of a row pass over n1 rows (xcd: NuHooks::row_map). A block's trials are k1 + n1 pos: the 8 or
+// 16 trials of one cache line of CS, CS0 or out belong to as many consecutive k1, and consecutive blocks are dealt
+// round-robin over the 8 XCDs, each with an L2 of its own -- every epilogue access would be a lone piece of a line
+// whose other pieces seven other L2s hold. With n1 a multiple of 8, blocks b = x (mod 8) take the contiguous rows
+// x n1/8 .. (x + 1) n1/8 - 1, so that a line's trials meet in one L2 (n1 = 8: the identity; rows move from n1 = 16 on).
+// A bijection of the rows whatever the placement: b mod 8 is a label chosen for speed, and no result depends on where
+// or when a block runs.
+__device__ __forceinline__ unsigned nu_row_of_block(unsigned b, unsigned n1, int xcd) {
+    return xcd && (n1 & 7u) == 0 ? (b & 7u) * (n1 >> 3) + (b >> 3) : b;
+}
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void k_nu_fft_rows_combine(const double2* __restrict__ X, int ll, int lnfft, int P,
                                                              int nrow, int64_t nf, int64_t jhi, int64_t h,
                                                              int64_t tbase, int64_t nbt, const double* __restrict__ bc,
-                                                             double2* __restrict__ CS) {
+                                                             double2* __restrict__ CS, int xcd) {
     extern __shared__ double2 nu_s[];
     __shared__ NuTile tw;
     const int lt = lnfft < 12 ? lnfft : 12;
     nu_tile_init(&tw, lt);
     const int64_t nfft = int64_t(1) << lnfft;
     const int L = 1 << ll, ln1 = lnfft - ll;
-    const int64_t k1 = blockIdx.x;
+    const int64_t k1 = nu_row_of_block(blockIdx.x, 1u << ln1, xcd);
     const int r = blockIdx.y;
     double2 acc[kNuFusedPer], nx[kNuFusedPer];
     NuBes bs[kNuFusedPer];
@@ -1428,14 +1438,14 @@ __global__ __launch_bounds__(1 << (LN2 - 3)) __attribute__((amdgpu_waves_per_eu(
 // their own stores. Moment sum as k_nu_rows_combine8 (rotating frame, doubled Bessel state, two moments per iteration).
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k_nu_rows_iw(
     const double2* X, int lnfft, int P, int plo, int accum, int nrow, int64_t nf, int64_t jhi, int64_t h,
-    int64_t tbase, int64_t nbt, const double* __restrict__ bc, double2* __restrict__ CS, const NuFinal F) {
+    int64_t tbase, int64_t nbt, const double* __restrict__ bc, double2* __restrict__ CS, const NuFinal F, int xcd) {
     constexpr int N = 4096, TPB = 512;
     extern __shared__ double2 nu_s[];  // [2][4096]
     __shared__ NuTile tw;
     nu_tile_init(&tw, 12);
     const int64_t nfft = int64_t(1) << lnfft;
     const int ln1 = lnfft - 12;
-    const int64_t k1b = blockIdx.x;
+    const int64_t k1b = nu_row_of_block(blockIdx.x, 1u << ln1, xcd);
     const int r = blockIdx.y;
     const int t = threadIdx.x, w = t >> 6, L = t & 63, hi3 = L >> 3, lo3 = L & 7;
     const int pos0 = w + 8 * hi3 + 64 * lo3;  // output positions pos0 + 512 q
@@ -2060,18 +2070,19 @@ struct NuRun {
             F.CS0 = CS;
         }
         const dim3 g2((unsigned)(int64_t(1) << ln1), (unsigned)b.nrow);
+        const int xcd = in.hooks.row_map;  // nu_row_of_block
         const int64_t jhi = pl.nseg - 1 - pl.h, tbase = b.rb * sh.nf + g.jbase - (b.tb0 + sh.first);
         double2* CSk = CS + (int64_t)(k - 1) * b.nbt;
         // plo = 0, accum = 0: all P moments in the one launch, the sum from zero (see the row kernels' comment)
         if (ln2 == 12 && !generic_fft)
             k_nu_rows_iw<<<g2, 512, 2 * lds_fft, s>>>(Z, lnfft, P, 0, 0, b.nrow, sh.nf, jhi, pl.h, tbase, b.nbt, tab.bc,
-                                                      CSk, F);
+                                                      CSk, F, xcd);
         else if (ln2 == 11 && !generic_fft)
             k_nu_rows_combine8<11><<<g2, 256, nu_rows_lds(11), s>>>(Z, lnfft, P, 0, 0, b.nrow, sh.nf, jhi, pl.h, tbase,
                                                                      b.nbt, tab.bc, CSk, F);
         else
             k_nu_fft_rows_combine<<<g2, 256, lds_fft, s>>>(Z, ln2, lnfft, P, b.nrow, sh.nf, jhi, pl.h, tbase, b.nbt,
-                                                           tab.bc, CSk);
+                                                           tab.bc, CSk, xcd);
         HIPCHK(hipGetLastError());
         HIPCHK(span(kNuClsPass2));
         return CRIMP_OK;

@@ -68,6 +68,7 @@ int main() {
     for (const double w : P.work) printf(" %a", w);
     printf("\n");
     ints("launches", P.launches, kNuCls);
+    printf("row_map %d\n", H.row_map);  // NuHooks' default (no case field, no plan field depends on it)
     for (const NuGroup& g : P.groups) {
         const NuPlan& pl = g.pl;
         printf("group %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %d %d %d %d %d %" PRId64 " %" PRId64
