@@ -242,7 +242,7 @@ static hipError_t h2d_async(hipStream_t s, void* d, const void* h, size_t bytes)
 // of a search) go through a page-locked per-thread buffer with one async copy and one stream sync: a blocking
 // pageable hipMemcpy of a few bytes after the sync cost ~30 us per readback (rocprofv3 sys-trace, profiles/r05).
 static hipError_t d2h(hipStream_t s, void* h, const void* d, size_t bytes) {
-    constexpr size_t kSmall = 4096;
+    constexpr size_t kSmall = 16384;  // (a folded NUFFT search's read-back block, search_nufft_finish.h)
     thread_local void* pin = nullptr;
     if (bytes <= kSmall) {
         if (!pin && hipHostMalloc(&pin, kSmall, hipHostMallocDefault) != hipSuccess) {
@@ -1977,6 +1977,7 @@ struct BestCand {
     double v;
     int64_t i;
 };
+static_assert(sizeof(BestCand) == 16, "NuFinCand (search_nufft_finish.h) mirrors BestCand");
 __device__ __forceinline__ bool best_better(double v1, int64_t i1, double v2, int64_t i2) {
     const bool n1 = isnan(v1), n2 = isnan(v2);
     if (n1 != n2) return n1;
@@ -2358,7 +2359,8 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
         bool done = false, best_done = false;
         const bool nu_try = nufft && nf >= 64;
         int* nuflags = nullptr;  // the NUFFT's device flags (fix-up count, photon order / plan check, best trial)
-        if (nu_try) HIPCHK(sc.alloc(&nuflags, 8));
+        // (the head of the block a folded search reads back in one transfer, search_nufft_finish.h)
+        if (nu_try) HIPCHK(sc.alloc(&nuflags, kNuFinBytes / sizeof(int)));
         NuSearchIn nu;
         nu.t = dtm;
         nu.t0 = t0;
@@ -2404,7 +2406,16 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
                 ex.check_order = gather_form ? 0 : 1;
             }
             progression = false;
-            int r = grid_is_progression(sc, s, dfr, nf, &ap, &progression, nufft ? dtm : nullptr, t0, n, nu_hs,
+            // A cached cell-gather plan with its start tables launches no check here: it rides in the search's first
+            // gather launch and the host finishes it from the search's read-back (nufft_search, NuRun::fold), or
+            // nufft_search queues these launches itself where the plan turns out to have no checking gather first.
+            nu.fold_try = from_cache && gather_form && cached.p && !nu.hooks.fold_off;
+            nu.ap = &ap;
+            int r = CRIMP_OK;
+            if (nu.fold_try)
+                progression = true;
+            else
+                r = grid_is_progression(sc, s, dfr, nf, &ap, &progression, nufft ? dtm : nullptr, t0, n, nu_hs,
                                         !gather_form, nuflags, from_cache ? &ex : nullptr);
             if (r) return r;
             if (!progression || !nu_try) return CRIMP_OK;  // the exact rule

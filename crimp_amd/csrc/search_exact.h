@@ -898,14 +898,15 @@ __global__ __launch_bounds__(256) void k_search_finalize_exact(const long long* 
 // block serialise at L2); k_ap_final reduces them. One pass of eight loads in flight per thread over up to
 // kApBlocks blocks: the whole 8 MB of a 1e6-trial grid is in flight at once (64 blocks with a loop: 14.7 us).
 constexpr int kApBlocks = 1024;
-__global__ __launch_bounds__(256) void k_ap_check(const double* __restrict__ f, int64_t nf, double2* __restrict__ part,
-                                                  int* __restrict__ zero) {
+// block b of nb of the check (256 threads): k_ap_check's body, and the check blocks that ride in a cached NUFFT
+// search's first gather launch (k_nu_gather, NuFold). Thread 0 returns the block's pair.
+__device__ __forceinline__ double2 ap_check_block(const double* __restrict__ f, int64_t nf, int b, int nb) {
     const double f0 = f[0];
     const double d = (f[nf - 1] - f0) / (double)(nf - 1);
     double dev = 0.0, fm = 0.0;
     constexpr int U = 8;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t j0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j0 < nf; j0 += U * stride) {
+    const int64_t stride = (int64_t)nb * 256;
+    for (int64_t j0 = (int64_t)b * 256 + threadIdx.x; j0 < nf; j0 += U * stride) {
         double v[U];
 #pragma unroll
         for (int q = 0; q < U; ++q) v[q] = f[j0 + q * stride < nf ? j0 + q * stride : nf - 1];
@@ -928,10 +929,15 @@ __global__ __launch_bounds__(256) void k_ap_check(const double* __restrict__ f, 
         red[1][threadIdx.x >> 6] = fm;
     }
     __syncthreads();
+    dev = fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]));
+    fm = fmax(fmax(red[1][0], red[1][1]), fmax(red[1][2], red[1][3]));
+    return make_double2(dev, fm);
+}
+__global__ __launch_bounds__(256) void k_ap_check(const double* __restrict__ f, int64_t nf, double2* __restrict__ part,
+                                                  int* __restrict__ zero) {
+    const double2 r = ap_check_block(f, nf, (int)blockIdx.x, (int)gridDim.x);
     if (threadIdx.x == 0) {
-        dev = fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]));
-        fm = fmax(fmax(red[1][0], red[1][1]), fmax(red[1][2], red[1][3]));
-        part[blockIdx.x] = make_double2(dev, fm);
+        part[blockIdx.x] = r;
         if (blockIdx.x == 0 && zero) *zero = 0;  // the NUFFT's order flag (k_nu_sorted ORs into it afterwards)
     }
 }

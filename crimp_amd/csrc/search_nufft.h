@@ -44,6 +44,7 @@
 
 #include "search_nufft_plan.h"  // the constants and kernel-argument structs the host plan fills (NuPass, NuCellArgs,
                                  // NuGatherSet), the plan itself (plan_nufft_search)
+#include "search_nufft_finish.h"  // the read-back block of a folded search and its finish on the host
 
 typedef double nu_f64x4 __attribute__((ext_vector_type(4)));
 
@@ -469,22 +470,60 @@ __device__ __forceinline__ double nu_quad_perm(double x) {
 // it the sums are those of fresh tables, and the order is the order k_nu_cellstart demands (cells ascend with dt).
 // A failing wave ORs 2 into *bad: the host drops the plan and redoes the search (nufft_search reads the flag first);
 // the kernels after this one then run on W that is wrong but in bounds -- every start lies in [0, n].
+// A folded search (NuFold::epoch != 0; NuRun::fold) launches nothing before its first gather, so nothing has zeroed
+// *bad: the kernel takes no entry test (a stale word would stop it), and a failing wave plain-stores the search's
+// epoch into bad[1] instead -- stores of one value cannot race, and a word left by an earlier search never equals
+// this search's epoch. Its first launch carries ncheck leading blocks that do k_ap_check's work on the trial grid
+// and leave before the cis table's fill and barrier: the lowest block indices, dispatched first, done while the
+// gather's waves run. Block 0 also publishes the plan's scalars as k_ap_final forms them and zeroes the fix-up count
+// bad[-1] (only later launches add to it) and the legacy flag bad[0] (nothing in a folded search reads or sets it
+// before the host does). The host finishes the check from the read-back (search_nufft_finish.h).
+struct NuFold {
+    int epoch = 0;   // 0: not folded
+    int ncheck = 0;  // leading check blocks of this launch
+    const double* f = nullptr;
+    int64_t nf = 0, n = 0;
+    double* pub = nullptr;    // [f[0], f[nf-1], t[0] - t0, t[n-1] - t0]
+    double2* part = nullptr;  // [ncheck] (max deviation, max |f|)
+};
 template <int R, bool TWOD, int PP, bool CHECK>  // PP >= P moments accumulated unconditionally (no per-moment selects)
 __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt, double t0,
                                                    const int64_t* __restrict__ startb, int64_t nfft, double s1,
                                                    double fch, double fcl, const double* __restrict__ c2row, int nrow,
                                                    int P, const NuGatherSet S, int* __restrict__ bad,
-                                                   const double2* __restrict__ tab, double2* __restrict__ Wb) {
-    // photons out of order (the cell starts found it): the start tables are not filled (nothing zeroes them), so no
-    // lane may read them; the search's results are discarded and the default path runs
-    if (*bad) return;
+                                                   const double2* __restrict__ tab, double2* __restrict__ Wb,
+                                                   const NuFold F) {
+    const bool folded = CHECK && F.epoch != 0;  // launch-uniform
+    int64_t blk = blockIdx.x;
+    if (folded) {
+        if (blk < F.ncheck) {  // block-uniform: a check block
+            const double2 r = ap_check_block(F.f, F.nf, (int)blk, F.ncheck);
+            if (threadIdx.x == 0) {
+                F.part[blk] = r;
+                if (blk == 0) {
+                    F.pub[0] = F.f[0];
+                    F.pub[1] = F.f[F.nf - 1];
+                    F.pub[2] = tt[0] - t0;
+                    F.pub[3] = tt[F.n - 1] - t0;
+                    bad[-1] = 0;
+                    bad[0] = 0;
+                }
+            }
+            return;
+        }
+        blk -= F.ncheck;
+    } else if (*bad) {
+        // photons out of order (the cell starts found it): the start tables are not filled (nothing zeroes them), so
+        // no lane may read them; the search's results are discarded and the default path runs
+        return;
+    }
     __shared__ double2 stab[2048];  // the cis table (nu_cis2), read per photon: LDS, not L2 latency
     for (int e = threadIdx.x; e < 2048; e += 256) stab[e] = tab[e];
     __syncthreads();
     int j = 0;  // this block's harmonic (block-uniform)
-    while (j + 1 < S.nk && (int64_t)blockIdx.x >= S.blk0[j + 1]) ++j;
+    while (j + 1 < S.nk && blk >= S.blk0[j + 1]) ++j;
     const int ll = S.lanes_log2[j], L = 1 << ll;
-    const int64_t tid = ((int64_t)blockIdx.x - S.blk0[j]) * 256 + threadIdx.x;
+    const int64_t tid = (blk - S.blk0[j]) * 256 + threadIdx.x;
     const int64_t idx = tid >> ll;
     const int sub = (int)(tid & (L - 1));
     if (idx >= S.gcount[j]) return;  // whole L-groups leave together (L divides 64); no barrier below
@@ -616,7 +655,12 @@ __global__ __launch_bounds__(256) void k_nu_gather(const double* __restrict__ tt
     }
     if (CHECK) {
         const unsigned long long failed = __ballot(fail);
-        if (failed && lane == __ffsll(failed) - 1) atomicOr(bad, 2);
+        if (failed && lane == __ffsll(failed) - 1) {
+            if (folded)
+                bad[1] = F.epoch;
+            else
+                atomicOr(bad, 2);
+        }
     }
     for (int o = L / 2; o > 0; o >>= 1)  // block-uniform L
 #pragma unroll
@@ -1659,10 +1703,11 @@ static void nu_launch_spread(int G, dim3 grid, hipStream_t s, const double* tt, 
 template <int R, bool TWOD, bool CHECK>
 static void launch_gather_r(int64_t blocks, const double* tt, double t0, const int64_t* start, int64_t nfft, double s1,
                             double fch, double fcl, const double* c2, int nrow, int P, const NuGatherSet& S,
-                            int* bad, const double2* tab, double2* W, hipStream_t s) {
-    const dim3 grid((unsigned)blocks);
-#define NU_GATHER(PPP) \
-    k_nu_gather<R, TWOD, PPP, CHECK><<<grid, 256, 0, s>>>(tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W)
+                            int* bad, const double2* tab, double2* W, const NuFold& F, hipStream_t s) {
+    const dim3 grid((unsigned)(blocks + (CHECK ? F.ncheck : 0)));
+#define NU_GATHER(PPP)                                                                                               \
+    k_nu_gather<R, TWOD, PPP, CHECK><<<grid, 256, 0, s>>>(tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, \
+                                                          W, F)
     if (P <= 14) {  // Z^2_m (m >= 2) at config-3-like grids (kNuEpsZm)
         NU_GATHER(14);
     } else if (P <= 15) {
@@ -1679,12 +1724,13 @@ static void launch_gather_r(int64_t blocks, const double* tt, double t0, const i
 // check: start is a cached plan's table, validated against the photons by the gather itself (k_nu_gather, CHECK)
 static void launch_gather(bool twod, bool check, int64_t blocks, const double* tt, double t0, const int64_t* start,
                           int64_t nfft, double s1, double fch, double fcl, const double* c2, int nrow, int P,
-                          const NuGatherSet& S, int* bad, const double2* tab, double2* W, hipStream_t s) {
+                          const NuGatherSet& S, int* bad, const double2* tab, double2* W, const NuFold& F,
+                          hipStream_t s) {
 #define NU_GATHER_R(RR, TD)                                                                                           \
     if (check)                                                                                                        \
-        launch_gather_r<RR, TD, true>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, s);     \
+        launch_gather_r<RR, TD, true>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, F, s);  \
     else                                                                                                              \
-        launch_gather_r<RR, TD, false>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, s)
+        launch_gather_r<RR, TD, false>(blocks, tt, t0, start, nfft, s1, fch, fcl, c2, nrow, P, S, bad, tab, W, F, s)
     if (twod) {
         NU_GATHER_R(kNuGatherRows, true);
     } else {
@@ -1881,9 +1927,16 @@ struct NuSearchIn {
     double* out = nullptr;
     double* best = nullptr;  // crimp_search_best's [power, index], or nullptr
     bool timed = false, no_fixup = false;
-    // [fix-up count, photons out of order (1; cell-gather plans) or a cached plan no longer valid (2), -, -, best power,
-    // best index (as doubles)], zeroed or set by k_ap_final, read back in one transfer at the end
+    // [fix-up count, photons out of order (1; cell-gather plans) or a cached plan no longer valid (2), a folded
+    // search's gather-failure epoch, -, best power, best index (as doubles)], zeroed or set by k_ap_final (a folded
+    // search: by its first gather), read back in one transfer at the end -- the head of a block of kNuFinBytes
+    // (search_nufft_finish.h) whose rest a folded search fills and reads back with it
     int* nflag = nullptr;
+    // The caller ran no progression check for this cached cell-gather plan (fold_try): nufft_search folds it into the
+    // first gather launch where the plan allows (NuRun::fold), and queues the check's own launches first where not
+    // (*ap then is the check's device block, as grid_is_progression leaves it).
+    bool fold_try = false;
+    double** ap = nullptr;
     const NuCellTab* cached = nullptr;  // a cached plan's start tables, or nullptr
     NuCellTab* keep = nullptr;          // receives the tables this search built for the plan cache
 };
@@ -1904,6 +1957,13 @@ struct NuRun {
     // search -- into memory the plan cache will own (cells_keep: every group's tables side by side) when the search
     // may be stored and they are under the cap, else into scratch, one group after the other in the same place.
     bool cells_reuse = false, cells_keep = false;
+    // A launch-time decision like cells_reuse (the plan is the same either way): a cached plan whose first launch is
+    // a checking gather runs no k_ap_check, k_ap_final or k_best_final launch. The check rides in that gather
+    // (NuFold), the best trial's candidates stay in the read-back block (best_host), and the host finishes both
+    // (search_nufft_finish.h). epoch: this search's, never 0.
+    bool fold = false, best_host = false;
+    int epoch = 0, ncheck = 0;
+    bool first_gather = true;
     double* U = nullptr;
     double2 *W = nullptr, *Y = nullptr, *CS = nullptr;
     int64_t *ctab = nullptr, *cstart = nullptr, *flagged = nullptr;
@@ -1947,7 +2007,10 @@ struct NuRun {
         HIPCHK(sc.alloc(&Y, (size_t)sp.Bmax));
         HIPCHK(sc.alloc(&CS, (size_t)sp.csmax));
         HIPCHK(sc.alloc(&flagged, (size_t)in.shape.count));
-        if (sp.best_alloc > 0) HIPCHK(sc.alloc(&best_part, (size_t)sp.best_alloc));
+        if (best_host)
+            best_part = reinterpret_cast<BestCand*>(reinterpret_cast<char*>(in.nflag) + kNuFinCandOff);
+        else if (sp.best_alloc > 0)
+            HIPCHK(sc.alloc(&best_part, (size_t)sp.best_alloc));
         if (!sp.passes.empty()) {
             HIPCHK(sc.alloc(&dps, sp.passes.size()));
             HIPCHK(hipMemcpyAsync(dps, sp.passes.data(), sp.passes.size() * sizeof(NuPass), hipMemcpyHostToDevice, s));
@@ -1978,8 +2041,20 @@ struct NuRun {
         const NuPlan& pl = g.pl;
         NuGatherSet S = set;
         for (int jj = 0; jj < S.nk; ++jj) S.soff[jj] += base;
+        NuFold F;
+        if (fold) {
+            char* blkp = reinterpret_cast<char*>(in.nflag);
+            F.epoch = epoch;
+            F.ncheck = first_gather ? ncheck : 0;  // the search's first launch carries the check
+            F.f = in.freq;
+            F.nf = in.shape.nf;
+            F.n = in.shape.n;
+            F.pub = reinterpret_cast<double*>(blkp + kNuFinPubOff);
+            F.part = reinterpret_cast<double2*>(blkp + kNuFinPartOff);
+        }
+        first_gather = false;
         launch_gather(in.twod, cells_reuse, S.blk0[S.nk], in.t, in.t0, cstart, int64_t(1) << pl.lnfft, pl.s1, pl.fch,
-                      pl.fcl, in.twod ? in.c2 + b.rb : nullptr, b.nrow, pl.P, S, in.nflag + 1, tab.cis2, W, s);
+                      pl.fcl, in.twod ? in.c2 + b.rb : nullptr, b.nrow, pl.P, S, in.nflag + 1, tab.cis2, W, F, s);
         HIPCHK(hipGetLastError());
         HIPCHK(span(kNuClsSpread));
         for (int jj = 0; jj < S.nk; ++jj) {
@@ -2152,10 +2227,30 @@ struct NuRun {
     }
 };
 
+// a search epoch: a per-process counter that is never 0 (calls are serialised, g_mutex)
+static int nu_next_epoch() {
+    static uint32_t e = 0;
+    if (++e == 0) ++e;
+    return (int)e;
+}
+
 static int nufft_search(Scratch& sc, hipStream_t s, const NuSearchIn& in, NuSearchOut* res) {
     *res = NuSearchOut{};
     const NuSearchShape& sh = in.shape;
     const NuSearchPlan sp = plan_nufft_search(in.hs, sh, in.hooks);
+    const bool cells_reuse = sp.applicable && sp.gather && in.cached && in.cached->p && in.cached->len == sp.starts_all;
+    // the fold needs a checking gather as the search's first launch
+    const bool fold = in.fold_try && cells_reuse && !sp.groups.empty() && !sp.groups[0].batches.empty() &&
+                      !sp.groups[0].batches[0].sets.empty();
+    if (in.fold_try && !fold) {  // the check's own launches, compared on the device (k_ap_final), no read-back
+        NuExpect ex{};
+        for (int q = 0; q < 4; ++q) ex.v[q] = in.hs[q];
+        ex.on = 1;
+        bool ok = false;
+        const int rc = grid_is_progression(sc, s, in.freq, sh.nf, in.ap, &ok, in.t, in.t0, sh.n, nullptr, false,
+                                           in.nflag, &ex);
+        if (rc) return rc;
+    }
     if (!sp.applicable) return CRIMP_OK;
     res->applicable = true;
     g_last_search_path = 2;
@@ -2170,7 +2265,13 @@ static int nufft_search(Scratch& sc, hipStream_t s, const NuSearchIn& in, NuSear
     }
     ARGCHK(in.hooks.lanes_valid(), "CRIMP_NUFFT_LANES must be 1, 2, 4 or 8");
     NuRun run(sc, s, in, sp);
-    run.cells_reuse = sp.gather && in.cached && in.cached->p && in.cached->len == sp.starts_all;
+    run.cells_reuse = cells_reuse;
+    run.fold = fold;
+    if (fold) {
+        run.epoch = nu_next_epoch();
+        run.ncheck = (int)std::min<int64_t>(cdiv(sh.nf, 256 * 8), kNuFinChecks);
+        run.best_host = in.best && sp.separate_batches == 0 && sp.best_count > 0 && sp.best_count <= kNuFinCands;
+    }
     run.cells_keep = sp.gather && !run.cells_reuse && in.keep && sp.starts_all > 0 && !in.hooks.plan_cache_off &&
                      !in.hooks.cell_cache_off && sp.starts_all * (int64_t)sizeof(int64_t) <= in.hooks.cell_cap &&
                      g_nu_cache.acquire(in.keep, sp.starts_all);
@@ -2180,7 +2281,7 @@ static int nufft_search(Scratch& sc, hipStream_t s, const NuSearchIn& in, NuSear
     if (!rc) rc = run.report_times();
     if (rc) return rc;
     // the best trial of the powers (crimp_search_best) rides on the same read-back; valid unless a fix-up follows
-    if (in.best) {
+    if (in.best && !run.best_host) {
         if (sp.separate_batches == 0 && sp.best_count > 0) {  // every batch finalized in its row pass: reduce their blocks
             k_best_final<<<1, 256, 0, s>>>(run.best_part, (int)sp.best_count, reinterpret_cast<double*>(in.nflag + 4));
             HIPCHK(hipGetLastError());
@@ -2190,10 +2291,36 @@ static int nufft_search(Scratch& sc, hipStream_t s, const NuSearchIn& in, NuSear
         }
     }
     int fl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(d2h(s, fl, in.nflag, (in.best ? 8 : 2) * sizeof(int)));
-    if (fl[1]) {  // photons out of order (found by the cell starts), or a cached plan that no longer holds (2):
-        res->applicable = false;  // nothing computed, the default path (or a fresh plan) runs
-        res->mismatch = (fl[1] & 2) != 0;
+    bool stale = false;
+    if (fold) {
+        // One read-back of the flags, the published scalars, the check's partials and the candidates; the host
+        // finishes the check and the best trial (search_nufft_finish.h). A plan that fails -- k_ap_final's test, or a
+        // gather wave that stored this search's epoch -- is what fl[1] & 2 is without the fold. The kernels of the
+        // failed attempt have then run to completion on stale scalars: in bounds, because the start tables are the
+        // cache's own with every index in [0, n] whatever the buffers hold now, and the key fixes the buffers and
+        // every shape; what they wrote is overwritten by the redo from a fresh plan.
+        alignas(16) static unsigned char hb[kNuFinBytes];  // (calls are serialised, g_mutex)
+        const size_t bytes = run.best_host ? kNuFinCandOff + (size_t)sp.best_count * sizeof(NuFinCand)
+                                           : kNuFinPartOff + (size_t)run.ncheck * 2 * sizeof(double);
+        HIPCHK(d2h(s, hb, in.nflag, bytes));
+        std::memcpy(fl, hb, sizeof(fl));
+        double dev = 0.0, fm = 0.0;
+        nu_finish_partials(reinterpret_cast<const double*>(hb + kNuFinPartOff), run.ncheck, &dev, &fm);
+        stale = fl[2] == run.epoch ||
+                !nu_finish_plan_ok(reinterpret_cast<const double*>(hb + kNuFinPubOff), sh.nf, dev, fm, in.hs);
+        if (run.best_host) {
+            const NuFinCand c = nu_finish_best(reinterpret_cast<const NuFinCand*>(hb + kNuFinCandOff), sp.best_count);
+            const double bv[2] = {c.v, (double)c.i};
+            std::memcpy(fl + 4, bv, sizeof(bv));
+        }
+    } else {
+        HIPCHK(d2h(s, fl, in.nflag, (in.best ? 8 : 2) * sizeof(int)));
+    }
+    // photons out of order (found by the cell starts), or a cached plan that no longer holds (2, stale): nothing
+    // computed, the default path (or a fresh plan) runs
+    if (fl[1] || stale) {
+        res->applicable = false;
+        res->mismatch = stale || (fl[1] & 2) != 0;
         g_last_search_path = 0;
         return CRIMP_OK;
     }

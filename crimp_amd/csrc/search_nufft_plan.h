@@ -102,6 +102,9 @@ struct NuHooks {
     bool separate_final = false;  // CRIMP_NUFFT_FINAL=separate: k_nu_finalize after every row batch, no fused finalize
     bool plan_cache_off = false;  // CRIMP_NUFFT_PLAN_CACHE=0: every search reads its plan back (A/B hook)
     bool cell_cache_off = false;  // CRIMP_NUFFT_CELL_CACHE=0: the plan is reused, its tables are rebuilt (A/B hook)
+    // CRIMP_NUFFT_FOLD=0: a cached cell-gather plan keeps its k_ap_check, k_ap_final and k_best_final launches (A/B
+    // hook; a launch-time choice of nufft_search, no plan field depends on it)
+    bool fold_off = false;
     // CRIMP_NUFFT_ROW_MAP=linear: block b of a row pass takes row b (0), not the XCD-contiguous map (1,
     // nu_row_of_block) -- the A/B hook and the tests' reference; the results are the same bits
     int row_map = 1;
@@ -133,6 +136,7 @@ struct NuHooks {
         h.separate_final = is("CRIMP_NUFFT_FINAL", "separate");
         h.plan_cache_off = is("CRIMP_NUFFT_PLAN_CACHE", "0");
         h.cell_cache_off = is("CRIMP_NUFFT_CELL_CACHE", "0");
+        h.fold_off = is("CRIMP_NUFFT_FOLD", "0");
         h.row_map = is("CRIMP_NUFFT_ROW_MAP", "linear") ? 0 : 1;
         h.set_budget(budget_env);
         return h;
