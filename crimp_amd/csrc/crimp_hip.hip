@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/crimp_hip.h"
+#include "search_plan.h"  // the host plans of the exact / fp64 searches and the constants they share with the kernels
 
 #define CRIMP_VERSION 2
 
@@ -527,9 +528,7 @@ __global__ __launch_bounds__(256) void k_search_prep(const double* __restrict__ 
 
 // Direct kernels: one lane per trial, every photon of its split broadcast to the wave through the scalar
 // path. Trial t of the launch is flat grid index first + (tidx ? tidx[t] : t). part layout: [split][2m][count]
-// (C_k at 2(k-1), S_k at 2(k-1)+1).
-constexpr int kSearchBlock = 256;
-constexpr int kSearchFold = 32;
+// (C_k at 2(k-1), S_k at 2(k-1)+1). kSearchBlock, kSearchFold: search_plan.h.
 
 __device__ __forceinline__ int64_t trial_index(const int64_t* __restrict__ tidx, int64_t first, int64_t t) {
     return first + (tidx ? tidx[t] : t);
@@ -1590,7 +1589,6 @@ __global__ __launch_bounds__(kSetBlock) void k_search_sets(const double* __restr
 // fp64 fix-up of a few trials over many photons (the exact path's flagged trials): block (t, split) sums the
 // harmonics k0 .. k0+G-1 of trial tidx[t] over photons of its split with fp64 sincospi of the exact phase of k0 and
 // fp64 angle addition (as k_search_f64), reduced across the block in a fixed order into part[split][2m][count].
-constexpr int kFixBlock = 256;
 template <int G, bool TWOD>
 __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
     const double* __restrict__ dt, const double* __restrict__ dt2, int64_t n, int64_t chunk,
@@ -1861,109 +1859,60 @@ extern "C" int crimp_binary_delay(const double* t_mjd, int64_t n, const crimp_ti
     return finish(s, flags);
 }
 
-template <bool TWOD>
-static void launch_f64(int G, dim3 grid, hipStream_t s, const double* dt, const double* dt2, int64_t n, int64_t chunk,
-                       const double* fr, int64_t nf, const double* c2, int64_t first, const int64_t* tidx,
-                       int64_t count, int k0, int ncomp, double* part) {
-#define CRIMP_LF(GG)                                                                                             \
-    k_search_f64<GG, TWOD><<<grid, kSearchBlock, 0, s>>>(dt, dt2, n, chunk, fr, nf, c2, first, tidx, count, k0, \
-                                                         ncomp, part)
-    if (G == 8) CRIMP_LF(8); else if (G == 4) CRIMP_LF(4); else if (G == 2) CRIMP_LF(2); else CRIMP_LF(1);
-#undef CRIMP_LF
-}
-
-// Per-trial device buffers of a search (fp64 per-split partial sums of the fp64 kernel, int64 totals of the exact
-// kernel) are bounded by this many bytes (CRIMP_SEARCH_BUDGET_MB, default 2048): a larger trial range
-// is computed in blocks of trials.
-static int64_t part_budget() {
-    static int64_t b = -1;
-    if (b < 0) {
-        const char* e = getenv("CRIMP_SEARCH_BUDGET_MB");
-        const long long mb = e ? atoll(e) : 2048;
-        b = (int64_t)(mb > 0 ? mb : 2048) << 20;
-    }
-    return b;
-}
-
-// Relative error the exact path certifies per trial before the fp64 fix-up (CRIMP_FIXUP_REL, default 1e-6; a
-// larger value is a test hook that sends more trials through the fix-up).
-static double fixup_rel() {
-    static double r = -1.0;
-    if (r < 0.0) {
-        const char* e = getenv("CRIMP_FIXUP_REL");
-        r = e ? atof(e) : 1e-6;
-        if (!(r > 0.0)) r = 1e-6;
-    }
-    return r;
-}
+// The instance K<G, TWOD> of an fp64 kernel (k_search_f64, k_search_f64_few) for a harmonic group G of harm_group
+#define CRIMP_F64_KERNEL(K, G, TWOD)                                                                \
+    ((TWOD) ? ((G) == 8 ? K<8, true> : (G) == 4 ? K<4, true> : (G) == 2 ? K<2, true> : K<1, true>) \
+            : ((G) == 8 ? K<8, false> : (G) == 4 ? K<4, false> : (G) == 2 ? K<2, false> : K<1, false>))
 
 // Direct (one lane per trial) fp64 search over trials first + (tidx ? tidx[t] : t), t < count, of any grid, into
-// out[t] (or out[tidx[t]] with scatter). The photon split count is a function of the photon count only.
+// out[t] (or out[tidx[t]] with scatter): plan_direct's photon splits and trial blocks.
 static int direct_search(Scratch& sc, hipStream_t s, const double* dt, const double* dt2, int64_t n,
                          const double* freq, int64_t nf, const double* c2, bool twod, int nharm, int stat,
                          int64_t first, const int64_t* tidx, int64_t count, double* out, bool scatter,
-                         KernelTimer* kt) {
-    const int64_t splits0 = std::max<int64_t>(1, std::min<int64_t>(64, n / 16384));
-    const int64_t chunk = cdiv(cdiv(n, splits0), kSearchFold) * kSearchFold;
-    const int64_t splits = cdiv(n, chunk);
+                         KernelTimer* kt, const SearchHooks& hooks) {
+    const DirectPlan P = plan_direct(n, nharm, count, hooks.budget);
     const int ncomp = 2 * nharm;
-    const int64_t cbmax = std::max<int64_t>(kSearchBlock, part_budget() / (8 * splits * ncomp));
-    const int64_t cb = std::min<int64_t>(count, cdiv(cdiv(count, cdiv(count, cbmax)), kSearchBlock) * kSearchBlock);
     double* part = nullptr;
-    HIPCHK(sc.alloc(&part, (size_t)(splits * ncomp * cb)));
+    HIPCHK(sc.alloc(&part, (size_t)(P.splits * ncomp * P.cb)));
     if (kt) kt->start();
-    for (int64_t b0 = 0; b0 < count; b0 += cb) {
-        const int64_t bc = std::min<int64_t>(cb, count - b0);
+    for (int64_t b0 = 0; b0 < count; b0 += P.cb) {
+        const int64_t bc = std::min<int64_t>(P.cb, count - b0);
         const int64_t* bt = tidx ? tidx + b0 : nullptr;
         const int64_t bfirst = tidx ? first : first + b0;
-        dim3 grid((unsigned)cdiv(bc, kSearchBlock), (unsigned)splits);
-        for (int k0 = 1; k0 <= nharm;) {  // groups of 8, 4, 2, 1 harmonics, each started from its exact phase
-            const int rem = nharm - k0 + 1;
-            const int G = rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1;
-            if (twod) launch_f64<true>(G, grid, s, dt, dt2, n, chunk, freq, nf, c2, bfirst, bt, bc, k0, ncomp, part);
-            else launch_f64<false>(G, grid, s, dt, dt2, n, chunk, freq, nf, c2, bfirst, bt, bc, k0, ncomp, part);
+        dim3 grid((unsigned)cdiv(bc, kSearchBlock), (unsigned)P.splits);
+        for (int k0 = 1, G; k0 <= nharm; k0 += G) {
+            G = harm_group(nharm - k0 + 1);
+            CRIMP_F64_KERNEL(k_search_f64, G, twod)<<<grid, kSearchBlock, 0, s>>>(dt, dt2, n, P.chunk, freq, nf, c2, bfirst,
+                                                                                   bt, bc, k0, ncomp, part);
             HIPCHK(hipGetLastError());
-            k0 += G;
         }
-        if (kt && b0 + cb >= count) kt->stop();
-        k_search_finalize<<<(unsigned)cdiv(bc, 256), 256, 0, s>>>(part, bc, (int)splits, nharm, stat, (double)n,
+        if (kt && b0 + P.cb >= count) kt->stop();
+        k_search_finalize<<<(unsigned)cdiv(bc, 256), 256, 0, s>>>(part, bc, (int)P.splits, nharm, stat, (double)n,
                                                                  scatter ? bt : nullptr, scatter ? out : out + b0);
         HIPCHK(hipGetLastError());
     }
     return CRIMP_OK;
 }
 
-// fp64 fix-up of the trials first + tidx[t] (t < count), a few trials over all photons: photon splits of >= 4096
-// photons (up to 1024), one block per (trial, split), the splits combined by k_search_finalize into out[tidx[t]].
+// fp64 fix-up of the trials first + tidx[t] (t < count), a few trials over all photons: plan_fixup's photon splits, one
+// block per (trial, split), the splits combined by k_search_finalize into out[tidx[t]].
 static int fixup_search(Scratch& sc, hipStream_t s, const double* dt, const double* dt2, int64_t n, const double* freq,
                         int64_t nf, const double* c2, bool twod, int nharm, int stat, int64_t first,
-                        const int64_t* tidx, int64_t count, double* out) {
-    const int64_t splits0 = std::max<int64_t>(1, std::min<int64_t>(1024, n / 4096));
-    const int64_t chunk = cdiv(n, splits0);
-    const int64_t splits = cdiv(n, chunk);
+                        const int64_t* tidx, int64_t count, double* out, const SearchHooks& hooks) {
+    const FixupPlan P = plan_fixup(n, nharm, hooks.budget);
     const int ncomp = 2 * nharm;
-    const int64_t cbmax = std::max<int64_t>(1, std::min<int64_t>(65535, part_budget() / (8 * splits * ncomp)));
     double* part = nullptr;
-    HIPCHK(sc.alloc(&part, (size_t)(splits * ncomp * std::min<int64_t>(count, cbmax))));
-    for (int64_t b0 = 0; b0 < count; b0 += cbmax) {
-        const int64_t bc = std::min<int64_t>(cbmax, count - b0);
-        dim3 grid((unsigned)bc, (unsigned)splits);
-        for (int k0 = 1; k0 <= nharm;) {
-            const int rem = nharm - k0 + 1;
-            const int G = rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1;
-#define CRIMP_FX(GG)                                                                                                \
-    if (twod)                                                                                                       \
-        k_search_f64_few<GG, true><<<grid, kFixBlock, 0, s>>>(dt, dt2, n, chunk, freq, nf, c2, first, tidx + b0, bc, \
-                                                              k0, ncomp, part);                                     \
-    else                                                                                                            \
-        k_search_f64_few<GG, false><<<grid, kFixBlock, 0, s>>>(dt, dt2, n, chunk, freq, nf, c2, first, tidx + b0,   \
-                                                               bc, k0, ncomp, part)
-            if (G == 8) { CRIMP_FX(8); } else if (G == 4) { CRIMP_FX(4); } else if (G == 2) { CRIMP_FX(2); } else { CRIMP_FX(1); }
-#undef CRIMP_FX
+    HIPCHK(sc.alloc(&part, (size_t)(P.splits * ncomp * std::min<int64_t>(count, P.cbmax))));
+    for (int64_t b0 = 0; b0 < count; b0 += P.cbmax) {
+        const int64_t bc = std::min<int64_t>(P.cbmax, count - b0);
+        dim3 grid((unsigned)bc, (unsigned)P.splits);
+        for (int k0 = 1, G; k0 <= nharm; k0 += G) {
+            G = harm_group(nharm - k0 + 1);
+            CRIMP_F64_KERNEL(k_search_f64_few, G, twod)<<<grid, kFixBlock, 0, s>>>(dt, dt2, n, P.chunk, freq, nf, c2, first,
+                                                                                    tidx + b0, bc, k0, ncomp, part);
             HIPCHK(hipGetLastError());
-            k0 += G;
         }
-        k_search_finalize<<<(unsigned)cdiv(bc, 256), 256, 0, s>>>(part, bc, (int)splits, nharm, stat, (double)n,
+        k_search_finalize<<<(unsigned)cdiv(bc, 256), 256, 0, s>>>(part, bc, (int)P.splits, nharm, stat, (double)n,
                                                                  tidx + b0, out);
         HIPCHK(hipGetLastError());
     }
@@ -2081,122 +2030,30 @@ static int grid_is_progression(Scratch& sc, hipStream_t s, const double* freq, i
 
 // Default path: the exact integer-MFMA kernel (search_exact.h) over an arithmetic-progression grid, then the
 // fp64 fix-up of the trials whose power is too small for the kernel's error bound (k_search_finalize_exact).
-// int64 totals in units of 2^-36 hold |C_k| <= n exactly for n < 2^27 photons; a larger search runs its photons in
-// chunks of < 2^27, each into its own totals, summed exactly by the finalize (periodsearch.py:57-71 has no limit).
-static const int64_t kExactMaxPhotons = int64_t(1) << 27;
-static const int64_t kExFoldMaxBlocks = 8192;  // fold scratch of one launch <= 1 GiB
-static const int64_t kExFoldPhotons = (int64_t)kExFold * kExChunk;  // photons between int64 folds (search_exact.h)
-static const int64_t kExNoFoldMaxBlocks = 131072;  // blocks per launch when splits need no fold scratch
-// Photon splits of the exact kernel (one 256-thread block per CU): >= 4096 photons per split and >= 8 rounds of
-// the device's CUs, and among those counts (up to 4x the smallest) the one whose last round of blocks is fullest:
-// a grid of 8.2 rounds runs as long as 9 (config 3: 123 block columns x 17 splits = 2091 blocks on 256 CUs wasted
-// 9 %; 29 splits = 3567 blocks fill 13.93 rounds).
-static void exact_splits(int64_t n, int64_t bpg, int64_t* chunk_out, int64_t* splits_out) {
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-            ncu = 256;
-    }
-    const int64_t smax_n = std::max<int64_t>(1, std::min<int64_t>(cdiv(n, 4096), 65535));
-    const int64_t srounds = cdiv(8 * (int64_t)ncu, bpg);
-    // Preferred: splits of <= kExFoldPhotons photons, which never fold into the int64 scratch (a block's only
-    // global traffic is then its final atomics, 128 KB; each intermediate fold would add 128 KB each way).
-    const int64_t snofold = cdiv(n, kExFoldPhotons);
-    static const bool long_splits = getenv("CRIMP_EXACT_LONG_SPLITS") != nullptr;  // test hook: the fold path
-    if (!long_splits && snofold <= 65535 && bpg * snofold <= kExNoFoldMaxBlocks) {
-        const int64_t lo = std::max<int64_t>(1, std::max<int64_t>(snofold, std::min<int64_t>(srounds, smax_n)));
-        int64_t best_chunk = 0, best_splits = 0;
-        double best_eff = -1.0;
-        for (int64_t want = lo; want <= std::min<int64_t>(smax_n, lo + lo / 4 + 1); ++want) {
-            const int64_t chunk = cdiv(cdiv(n, want), kExChunk) * kExChunk;
-            const int64_t splits = cdiv(n, chunk);
-            const int64_t blocks = bpg * splits;
-            const double eff = (double)blocks / (double)(cdiv(blocks, ncu) * ncu);
-            if (chunk <= kExFoldPhotons && eff > best_eff + 0.005) {
-                best_eff = eff;
-                best_chunk = chunk;
-                best_splits = splits;
-            }
-        }
-        if (best_splits > 0) {
-            *chunk_out = best_chunk;
-            *splits_out = best_splits;
-            return;
-        }
-    }
-    const int64_t smax = std::max<int64_t>(1, std::min<int64_t>(smax_n, kExFoldMaxBlocks / bpg));
-    const int64_t smin = std::max<int64_t>(1, std::min<int64_t>(srounds, smax));
-    int64_t best_chunk = 0, best_splits = 0;
-    double best_eff = -1.0;
-    for (int64_t want = smin; want <= std::min<int64_t>(smax, 4 * smin); ++want) {
-        const int64_t chunk = cdiv(cdiv(n, want), kExChunk) * kExChunk;
-        const int64_t splits = cdiv(n, chunk);
-        const int64_t blocks = bpg * splits;
-        const double eff = (double)blocks / (double)(cdiv(blocks, ncu) * ncu);
-        if (eff > best_eff + 0.005) {
-            best_eff = eff;
-            best_chunk = chunk;
-            best_splits = splits;
-        }
-    }
-    *chunk_out = best_chunk;
-    *splits_out = best_splits;
-}
-
+// plan_exact (search_plan.h) decides the photon chunks, the trial blocks and every launch's photon splits.
 static int exact_search(Scratch& sc, hipStream_t s, const double* dt, const double* dt2, int64_t n, const double* freq,
                         int64_t nf, const double* c2, const double* ap, bool twod, int nharm, int stat, int64_t first,
-                        int64_t count, double* out, KernelTimer* kt, int64_t* nfixed, bool no_fixup) {
-    const int64_t tpr = cdiv(nf, kExTileTrials);
+                        int64_t count, double* out, KernelTimer* kt, int64_t* nfixed, bool no_fixup,
+                        const SearchHooks& hooks) {
+    static const int64_t ncu = nu_cus();  // once per process
+    const ExactPlan P = plan_exact(n, nf, nharm, first, count, ncu, hooks);
+    if (P.err) return set_err(P.err, P.msg);
+    const int64_t nchunk = P.nchunk, pc = P.pc;
+    const auto kernel = twod ? k_search_exact<true> : k_search_exact<false>;
     const int ncomp = 2 * nharm;
-    // photon chunks of < 2^27 (one for every search below that), each with its own int64 totals
-    const int64_t nchunk = cdiv(n, kExactMaxPhotons - 1);
-    const int64_t pc = cdiv(n, nchunk);
-    // Trial blocks are bounded by the int64 totals buffer (part_budget) and by the tiles one launch may hold
-    // (<= kExFoldMaxBlocks block columns, so that a fold scratch stays <= 1 GiB: a 2-D grid's rows each start a
-    // new tile, so a block of short rows holds more tiles than its trial count suggests); whole tiles.
-    int64_t want = std::max<int64_t>(kExTileTrials, part_budget() / (8 * ncomp * nchunk)), cb = 0;
-    struct Blk { int64_t bfirst, bcount, tf, nt, bpg, chunk, splits; };
-    std::vector<Blk> blks;
-    int64_t fold_blocks = 0;  // the largest bpg * splits of the blocks whose splits fold into the int64 scratch
-    for (;;) {
-        cb = std::min<int64_t>(count, cdiv(cdiv(count, cdiv(count, want)), kExTileTrials) * kExTileTrials);
-        blks.clear();
-        fold_blocks = 0;
-        bool fits = true;
-        for (int64_t b0 = 0; b0 < count && fits; b0 += cb) {
-            Blk k;
-            k.bfirst = first + b0;
-            k.bcount = std::min<int64_t>(cb, count - b0);
-            const int64_t last = k.bfirst + k.bcount - 1;
-            k.tf = (k.bfirst / nf) * tpr + (k.bfirst % nf) / kExTileTrials;
-            const int64_t tl = (last / nf) * tpr + (last % nf) / kExTileTrials;
-            k.nt = tl - k.tf + 1;
-            k.bpg = cdiv(k.nt, kExWaves);
-            fits = k.bpg <= kExFoldMaxBlocks;
-            exact_splits(pc, k.bpg, &k.chunk, &k.splits);
-            if (k.chunk > kExFoldPhotons) fold_blocks = std::max<int64_t>(fold_blocks, k.bpg * k.splits);
-            blks.push_back(k);
-        }
-        if (fits) break;
-        if (cb <= kExTileTrials) return set_err(CRIMP_ERR_ARG, "exact search: trial block does not fit one launch");
-        want = cb / 2;
-    }
-    if (fold_blocks > kExFoldMaxBlocks) return set_err(CRIMP_ERR_HIP, "exact search: fold scratch bound");
     unsigned long long* tot = nullptr;
     long long* fold = nullptr;
     int64_t* flagged = nullptr;
     int* nflag = nullptr;
-    HIPCHK(sc.alloc(&tot, (size_t)(ncomp * cb * nchunk)));
-    HIPCHK(sc.alloc(&flagged, (size_t)count));
+    HIPCHK(sc.alloc(&tot, (size_t)P.tot_elems));
+    HIPCHK(sc.alloc(&flagged, (size_t)P.flagged_elems));
     HIPCHK(sc.alloc(&nflag, 1));
-    // fold scratch only when some block's splits are longer than one fold period; shorter splits never touch it
-    if (fold_blocks > 0) HIPCHK(sc.alloc(&fold, (size_t)(fold_blocks * kExWaves * kExFoldVals * 64)));
+    if (P.fold_elems > 0) HIPCHK(sc.alloc(&fold, (size_t)P.fold_elems));
     HIPCHK(hipMemsetAsync(nflag, 0, sizeof(int), s));
     const double sigc = std::sqrt((double)n) * 1e-9;  // standard deviation of the error of C_k (search_exact.h)
     if (kt) kt->start();
-    for (size_t bi = 0; bi < blks.size(); ++bi) {
-        const Blk& k = blks[bi];
+    for (size_t bi = 0; bi < P.blocks.size(); ++bi) {
+        const ExBlock& k = P.blocks[bi];
         const int64_t b0 = k.bfirst - first;
         const int64_t cstride = (int64_t)ncomp * k.bcount;  // one chunk's totals
         HIPCHK(hipMemsetAsync(tot, 0, (size_t)(cstride * nchunk) * sizeof(unsigned long long), s));
@@ -2205,28 +2062,22 @@ static int exact_search(Scratch& sc, hipStream_t s, const double* dt, const doub
             const int64_t p0 = pch * pc, np_ = std::min<int64_t>(pc, n - p0);
             unsigned long long* tc = tot + pch * cstride;
             for (int h = 1; h <= nharm; ++h) {
-                if (twod)
-                    k_search_exact<true><<<grid, kExBlock, 0, s>>>(dt + p0, dt2 ? dt2 + p0 : nullptr, np_, k.chunk, freq,
-                                                                   nf, c2, ap, k.tf, k.nt, tpr, k.bfirst, k.bcount, h, tc,
-                                                                   fold);
-                else
-                    k_search_exact<false><<<grid, kExBlock, 0, s>>>(dt + p0, dt2 ? dt2 + p0 : nullptr, np_, k.chunk,
-                                                                    freq, nf, c2, ap, k.tf, k.nt, tpr, k.bfirst, k.bcount,
-                                                                    h, tc, fold);
+                kernel<<<grid, kExBlock, 0, s>>>(dt + p0, dt2 ? dt2 + p0 : nullptr, np_, k.chunk, freq, nf, c2, ap, k.tf,
+                                                 k.nt, P.tpr, k.bfirst, k.bcount, h, tc, fold);
                 HIPCHK(hipGetLastError());
             }
         }
-        if (kt && bi + 1 == blks.size()) kt->stop();
+        if (kt && bi + 1 == P.blocks.size()) kt->stop();
         k_search_finalize_exact<<<(unsigned)cdiv(k.bcount, 256), 256, 0, s>>>(
-            reinterpret_cast<const long long*>(tot), k.bcount, nharm, stat, (double)n, sigc, fixup_rel(), b0, out + b0,
-            nflag, flagged, (int)nchunk, cstride);
+            reinterpret_cast<const long long*>(tot), k.bcount, nharm, stat, (double)n, sigc, hooks.fixup_rel, b0,
+            out + b0, nflag, flagged, (int)nchunk, cstride);
         HIPCHK(hipGetLastError());
     }
     int nf_h = 0;
     HIPCHK(d2h(s, &nf_h, nflag, sizeof(int)));
     *nfixed = nf_h;
     if (nf_h == 0 || no_fixup) return CRIMP_OK;
-    return fixup_search(sc, s, dt, dt2, n, freq, nf, c2, twod, nharm, stat, first, flagged, nf_h, out);
+    return fixup_search(sc, s, dt, dt2, n, freq, nf, c2, twod, nharm, stat, first, flagged, nf_h, out, hooks);
 }
 
 extern "C" int crimp_best(const double* x, int64_t n, double* best, uint32_t flags, void* stream) {
@@ -2376,6 +2227,7 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
         nu.shape.count = count;
         nu.shape.want_best = best != nullptr;
         nu.hooks = NuHooks::from_env();
+        nu.search_hooks = SearchHooks::from_env();
         nu.hs = nu_hs;
         nu.out = dout;
         nu.best = best;
@@ -2450,12 +2302,12 @@ static int search_impl(const double* t, int64_t n, double t0, const double* freq
             g_last_search_path = 1;
             int64_t nfix = 0;
             rc = exact_search(sc, s, ddt, ddt2, n, dfr, nf, dc2, ap, twod, nharm, stat, first, count, dout, &kt, &nfix,
-                              (flags & CRIMP_FLAG_NO_FIXUP) != 0);
+                              (flags & CRIMP_FLAG_NO_FIXUP) != 0, nu.search_hooks);
             g_last_fixups = nfix;
         } else {
             g_last_search_path = 0;
             rc = direct_search(sc, s, ddt, ddt2, n, dfr, nf, dc2, twod, nharm, stat, first, nullptr, count, dout,
-                               false, &kt);
+                               false, &kt, nu.search_hooks);
         }
         if (rc) return rc;
         if (best && !best_done) {  // the exact / fp64 paths, or a NUFFT whose fix-up rewrote powers after its read-back

@@ -1923,6 +1923,7 @@ struct NuSearchIn {
     bool twod = false;
     NuSearchShape shape;
     NuHooks hooks;
+    SearchHooks search_hooks;  // the fix-up threshold and the fix-up's budget (search_plan.h)
     const double* hs = nullptr;  // [delta, f0, dt[0], dt[n-1], unsorted flag (int bits)] (plan_nufft_search)
     double* out = nullptr;
     double* best = nullptr;  // crimp_search_best's [power, index], or nullptr
@@ -2135,7 +2136,7 @@ struct NuRun {
             F.Pc = P;
             F.nph = (double)sh.n;
             F.invfact = pl.invfact;
-            F.rel = fixup_rel();
+            F.rel = in.search_hooks.fixup_rel;
             F.tb0 = b.tb0;
             F.out = in.out;
             F.nflag = in.nflag;
@@ -2167,7 +2168,7 @@ struct NuRun {
         const NuSearchShape& sh = in.shape;
         k_nu_finalize<<<(unsigned)cdiv(b.nbt, 256), 256, 0, s>>>(CS, b.nbt, sh.nharm, sh.stat, (double)sh.n, sh.nf, g.jbase,
                                                                  int64_t(1) << g.pl.lnfft, g.pl.P, g.pl.invfact,
-                                                                 fixup_rel(), b.tb0, sh.first, in.out, in.nflag, flagged);
+                                                                 in.search_hooks.fixup_rel, b.tb0, sh.first, in.out, in.nflag, flagged);
         HIPCHK(hipGetLastError());
         HIPCHK(span(kNuClsFinalize));
         return CRIMP_OK;
@@ -2337,5 +2338,5 @@ static int nufft_search(Scratch& sc, hipStream_t s, const NuSearchIn& in, NuSear
     k_search_prep<<<(int)std::min<int64_t>(cdiv(sh.n, 256), 4096), 256, 0, s>>>(in.t, sh.n, in.t0, dt, dt2);
     HIPCHK(hipGetLastError());
     return fixup_search(sc, s, dt, dt2, sh.n, in.freq, sh.nf, in.c2, in.twod, sh.nharm, sh.stat, sh.first, run.flagged, nf_h,
-                        in.out);
+                        in.out, in.search_hooks);
 }

@@ -186,8 +186,8 @@ def test_trial_blocks_and_fixup(gpu, monkeypatch):
     idx = np.array([0, 450_000, 450_559, 450_560, 450_561, M - 1])
     hr = O.search(t_h, f_h[idx], 20, stat="h")
     assert _rel_err(h[idx], hr).max() <= 1e-6
-    # fix-up: a 2048-trial window in a fresh process-level setting (the thresholds are read once per process,
-    # so the hook is exercised through a subprocess)
+    # fix-up: a 2048-trial window in a child process with the threshold hook in its environment (the hooks are read
+    # at the start of every search; tests/test_gpu_search_blocks.py flips them inside one process)
     import subprocess
     import sys
     code = ("import sys, numpy as np; sys.path.insert(0, %r); from crimp_amd import ops, _native as N; "
