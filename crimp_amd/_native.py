@@ -67,7 +67,9 @@ SHAPE_SUMS = 4 + 3 * MAX_COMP  # CRIMP_SHAPE_SUMS
 
 FIT_MAX_DIM = 32
 FIT_WAVES_FIXED, FIT_WAVES_ONLY, FIT_WAVES_MIXED = 0, 1, 2
-FIT_SLOT_F, FIT_SLOT_GLITCH, FIT_SLOT_WAVE = 0, 1, 2
+FIT_SLOT_F, FIT_SLOT_GLITCH, FIT_SLOT_WAVE, FIT_SLOT_BINARY = 0, 1, 2, 3
+# CRIMP_ORBIT_*: the orbit field a FIT_SLOT_BINARY slot corrects (T0 stands for TASC under ELL1)
+ORBIT_FIELDS = ("PB", "A1", "T0", "ECC", "OM", "OMDOT", "GAMMA", "EPS1", "EPS2", "PBDOT", "A1DOT")
 
 
 class FitSlot(ctypes.Structure):
@@ -100,7 +102,7 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
            "crimp_gather_ranges", "crimp_sim_events", "crimp_binary_delay", "crimp_photon_tile", "crimp_photon_nll",
-           "crimp_photon_mcmc")
+           "crimp_photon_mcmc", "crimp_orbit_nll", "crimp_orbit_mcmc")
 
 _lib = None
 _lock = threading.Lock()
@@ -146,6 +148,9 @@ def load(require_device=True):
             L.crimp_timing_nll.argtypes = [P, P, P, P, i64, MP, MP, FP, P, i64, P, P, u32, P]
             L.crimp_timing_mcmc.argtypes = [P, P, P, P, i64, MP, MP, FP, P, P, P, i32, i64, ctypes.c_uint64, i64, P, P, P,
                                             u32, P]
+            L.crimp_orbit_nll.argtypes = [P, P, P, P, i64, MP, MP, MP, FP, P, i64, P, P, u32, P]
+            L.crimp_orbit_mcmc.argtypes = [P, P, P, P, i64, MP, MP, MP, FP, P, P, P, i32, i64, ctypes.c_uint64, i64, P, P,
+                                           P, u32, P]
             TP = ctypes.POINTER(Template)
             L.crimp_photon_tile.argtypes = []
             L.crimp_photon_nll.argtypes = [P, P, i64, MP, FP, TP, ctypes.c_double, i32, P, i64, P, P, u32, P]

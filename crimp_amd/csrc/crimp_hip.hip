@@ -1647,6 +1647,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "toa_shape.h"
 #include "phase_cube.h"
 #include "timing_fit.h"
+#include "orbit_fit.h"
 #include "sim_events.h"
 #include "photon_fit.h"
 
@@ -3214,16 +3215,19 @@ extern "C" int crimp_phase_cube(const double* x, int64_t n, const crimp_timing_m
 }
 
 // ---- timing-model fits of ToAs (timing_fit.h)
-// the kernels' form of the per-problem models and of the map, with every check of crimp_timing_nll / _mcmc on them
+// the kernels' form of the per-problem models and of the map, with every check of crimp_timing_nll / _mcmc on them.
+// orbit_fields (crimp_orbit_nll / _mcmc; else null): BINARY slots are admitted, the mask of the orbit fields they name
+// is returned there, and the bases' binary blocks are not read.
 static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_model* fit_base,
                       const crimp_timing_model* wave_base, const crimp_fit_map* map, std::vector<TFModel>* models,
-                      TFMap* dm) {
+                      TFMap* dm, uint32_t* orbit_fields = nullptr) {
     ARGCHK(nprob >= 1 && nprob <= (int64_t(1) << 24), "nprob out of range");
     ARGCHK(fit_base != nullptr && wave_base != nullptr && map != nullptr, "null argument");
     ARGCHK(map->ndim >= 1 && map->ndim <= CRIMP_FIT_MAX_DIM, "ndim must be 1..CRIMP_FIT_MAX_DIM");
     ARGCHK(map->branch >= CRIMP_FIT_WAVES_FIXED && map->branch <= CRIMP_FIT_WAVES_MIXED, "unknown branch");
     ARGCHK(map->f0_param >= -1 && map->f0_param < map->ndim, "f0_param out of range");
     *dm = TFMap{};
+    if (orbit_fields) *orbit_fields = 0;
     dm->ndim = map->ndim;
     dm->f0_param = map->f0_param;
     double fact = 1.0;
@@ -3246,6 +3250,12 @@ static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_mo
                    "slot names a wave field outside the model");
             ARGCHK(map->branch != CRIMP_FIT_WAVES_FIXED, "a wave slot with CRIMP_FIT_WAVES_FIXED");
             top_wv = std::max(top_wv, sl.index);
+        } else if (sl.kind == CRIMP_FIT_SLOT_BINARY) {
+            ARGCHK(orbit_fields != nullptr, "a BINARY slot: crimp_orbit_nll and crimp_orbit_mcmc fit the orbit");
+            ARGCHK(sl.index >= 0 && sl.index < kOfFields,
+                   "slot names an orbit field outside CRIMP_ORBIT_PB..CRIMP_ORBIT_A1DOT");
+            ARGCHK(!(*orbit_fields >> sl.index & 1u), "two slots name one orbit field");
+            *orbit_fields |= 1u << sl.index;
         } else {
             return set_err(CRIMP_ERR_ARG, "unknown slot kind");
         }
@@ -3261,7 +3271,8 @@ static int tf_prepare(const int64_t* h_off, int64_t nprob, const crimp_timing_mo
         ARGCHK(fm.n_glitch >= 0 && fm.n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
         ARGCHK(fm.n_wave >= 0 && fm.n_wave <= CRIMP_MAX_WAVE && wm.n_wave >= 0 && wm.n_wave <= CRIMP_MAX_WAVE,
                "n_wave out of range");
-        ARGCHK(fm.binary == CRIMP_BINARY_NONE && wm.binary == CRIMP_BINARY_NONE, "binary models are not fitted yet");
+        ARGCHK(orbit_fields != nullptr || (fm.binary == CRIMP_BINARY_NONE && wm.binary == CRIMP_BINARY_NONE),
+               "binary models are not fitted yet");
         ARGCHK(top_gl < fm.n_glitch, "slot names a glitch outside the model");
         ARGCHK(top_wv < fm.n_wave, "slot names a wave harmonic outside the model");
         TFModel& tm = (*models)[(size_t)i];
@@ -3396,6 +3407,186 @@ extern "C" int crimp_timing_mcmc(const double* t_mjd, const double* y, const dou
         kt.start();
         k_timing_mcmc<<<(unsigned)nprob, kTfMcWaves * 64, lds, s>>>(dt, dy, de, doff, dmod, dmap, dp0, dlo, dhi, (int)W,
                                                                     steps, seed, first_problem, stage, dchain, dlp, dacc);
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, chain, dchain, rows * nd, dev));
+        HIPCHK(copy_back(s, logprob, dlp, rows, dev));
+        HIPCHK(copy_back(s, accepted, dacc, (size_t)nprob * w, dev));
+    }
+    return finish(s, flags);
+}
+
+// ---- timing-model fits of ToAs under a binary orbit (orbit_fit.h)
+// What both calls hold after their host checks: the offsets, the problems' models in the kernels' form, the par spin
+// models of the prologue and the map
+struct OFCall {
+    std::vector<int64_t> h_off;
+    std::vector<OFModel> models;
+    std::vector<CPModel> parm;
+    TFMap dm;
+};
+
+static int of_prepare(const Call& call, const int64_t* offsets, int64_t nprob, const crimp_timing_model* par,
+                      const crimp_timing_model* fit_base, const crimp_timing_model* wave_base,
+                      const crimp_fit_map* map, OFCall* c) {
+    ARGCHK(par != nullptr, "null argument");
+    int rc = tf_host_offsets(call, offsets, nprob, &c->h_off);
+    if (rc != CRIMP_OK) return rc;
+    std::vector<TFModel> tf;
+    uint32_t fields = 0;
+    rc = tf_prepare(c->h_off.data(), nprob, fit_base, wave_base, map, &tf, &c->dm, &fields);
+    if (rc != CRIMP_OK) return rc;
+    constexpr uint32_t bt_only = 1u << CRIMP_ORBIT_ECC | 1u << CRIMP_ORBIT_OM | 1u << CRIMP_ORBIT_OMDOT |
+                                 1u << CRIMP_ORBIT_GAMMA;
+    constexpr uint32_t ell1_only = 1u << CRIMP_ORBIT_EPS1 | 1u << CRIMP_ORBIT_EPS2;
+    c->models.resize((size_t)nprob);
+    c->parm.resize((size_t)nprob);
+    for (int64_t i = 0; i < nprob; ++i) {
+        const crimp_timing_model& pm = par[i];
+        ARGCHK(pm.binary != CRIMP_BINARY_NONE, "the model has no binary");
+        rc = check_binary(&pm);
+        if (rc != CRIMP_OK) return rc;
+        ARGCHK(!(fields & (pm.binary == CRIMP_BINARY_BT ? ell1_only : bt_only)),
+               "slot names an orbit field the model's kind does not have");
+        ARGCHK(pm.n_glitch >= 0 && pm.n_glitch <= CRIMP_MAX_GLITCH, "n_glitch out of range");
+        ARGCHK(pm.n_wave >= 0 && pm.n_wave <= CRIMP_MAX_WAVE, "n_wave out of range");
+        OFModel& m = c->models[(size_t)i];
+        m.tf = tf[(size_t)i];
+        m.ob = OFOrbit{};
+        m.ob.kind = pm.binary;
+        double* r = m.ob.raw;
+        r[CRIMP_ORBIT_PB] = pm.bin_pb;
+        r[CRIMP_ORBIT_A1] = pm.bin_a1;
+        r[CRIMP_ORBIT_T0] = pm.bin_t0;
+        r[CRIMP_ORBIT_ECC] = pm.bin_ecc;
+        r[CRIMP_ORBIT_OM] = pm.bin_om;
+        r[CRIMP_ORBIT_OMDOT] = pm.bin_omdot;
+        r[CRIMP_ORBIT_GAMMA] = pm.bin_gamma;
+        r[CRIMP_ORBIT_EPS1] = pm.bin_eps1;
+        r[CRIMP_ORBIT_EPS2] = pm.bin_eps2;
+        r[CRIMP_ORBIT_PBDOT] = pm.bin_pbdot;
+        r[CRIMP_ORBIT_A1DOT] = pm.bin_a1dot;
+        make_cpmodel(&pm, 7, &c->parm[(size_t)i]);
+    }
+    return CRIMP_OK;
+}
+
+// the device copies of an OFCall and the room of the per-ToA constants
+static hipError_t of_upload(Scratch& sc, const OFCall& c, size_t ntoa, OFModel** dmod, CPModel** dparp, TFMap** dmap,
+                            double** dconst) {
+    CPModel*& dpar = *dparp;
+    hipError_t e;
+    if ((e = sc.alloc(dmod, c.models.size())) != hipSuccess) return e;
+    if ((e = sc.alloc(&dpar, c.parm.size())) != hipSuccess) return e;
+    if ((e = sc.alloc(dmap, 1)) != hipSuccess) return e;
+    if ((e = sc.alloc(dconst, 3 * ntoa)) != hipSuccess) return e;
+    if ((e = h2d(*dmod, c.models.data(), c.models.size() * sizeof(OFModel))) != hipSuccess) return e;
+    if ((e = h2d(dpar, c.parm.data(), c.parm.size() * sizeof(CPModel))) != hipSuccess) return e;
+    return h2d(*dmap, &c.dm, sizeof(TFMap));
+}
+
+extern "C" int crimp_orbit_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                               int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                               const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec,
+                               int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
+    ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && pvec != nullptr && nll != nullptr, "null argument");
+    ARGCHK(P >= 1 && P <= (int64_t(1) << 24), "P out of range");
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    OFCall c;
+    const int rc = of_prepare(call, offsets, nprob, par, fit_base, wave_base, map, &c);
+    if (rc != CRIMP_OK) return rc;
+    const int64_t groups = cdiv(P, kTfNllWaves);
+    ARGCHK(nprob * groups <= (int64_t(1) << 30), "too many parameter vectors for one launch");
+    const size_t ntoa = (size_t)c.h_off[(size_t)nprob], nd = (size_t)c.dm.ndim;
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp = nullptr;
+        const int64_t* doff = nullptr;
+        double *dnll = nullptr, *dmu = nullptr, *dconst = nullptr;
+        OFModel* dmod = nullptr;
+        CPModel* dpar = nullptr;
+        TFMap* dmap = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
+        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
+        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
+        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
+        HIPCHK(stage_in(sc, pvec, (size_t)nprob * (size_t)P * nd, dev, &dp));
+        HIPCHK(stage_out(sc, nll, (size_t)nprob * (size_t)P, dev, &dnll));
+        HIPCHK(stage_out(sc, mu, (size_t)P * ntoa, dev, &dmu));
+        HIPCHK(of_upload(sc, c, ntoa, &dmod, &dpar, &dmap, &dconst));
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();  // the prologue is part of a call's cost
+        k_orbit_prologue<<<(unsigned)nprob, 256, 0, s>>>(dt, doff, dmod, dpar, (int64_t)ntoa, dconst);
+        HIPCHK(hipGetLastError());
+        k_orbit_nll<<<(unsigned)(nprob * groups), kTfNllWaves * 64, 0, s>>>(dt, dy, de, dconst, (int64_t)ntoa, doff, dmod,
+                                                                            dmap, dp, P, groups, dnll, dmu);
+        HIPCHK(hipGetLastError());
+        kt.stop();
+        HIPCHK(copy_back(s, nll, dnll, (size_t)nprob * (size_t)P, dev));
+        HIPCHK(copy_back(s, mu, dmu, (size_t)P * ntoa, dev));
+    }
+    return finish(s, flags);
+}
+
+extern "C" int crimp_orbit_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                                int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                                const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
+                                const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                                int64_t first_problem, double* chain, double* logprob, int64_t* accepted,
+                                uint32_t flags, void* stream) {
+    ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && p0 != nullptr && lo != nullptr && hi != nullptr &&
+               chain != nullptr && logprob != nullptr && accepted != nullptr, "null argument");
+    ARGCHK(map != nullptr && map->ndim >= 1 && map->ndim <= CRIMP_FIT_MAX_DIM, "ndim must be 1..CRIMP_FIT_MAX_DIM");
+    ARGCHK(W >= 2 && W % 2 == 0 && W <= 256 && W >= 2 * map->ndim, "walkers: even, >= 2 ndim and <= 256");
+    ARGCHK(steps >= 1 && steps <= (int64_t(1) << 31), "steps out of range");
+    ARGCHK(first_problem >= 0 && first_problem + nprob <= (int64_t(1) << 32), "first_problem out of range");
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    OFCall c;
+    const int rc = of_prepare(call, offsets, nprob, par, fit_base, wave_base, map, &c);
+    if (rc != CRIMP_OK) return rc;
+    const size_t ntoa = (size_t)c.h_off[(size_t)nprob], nd = (size_t)c.dm.ndim, w = (size_t)W;
+    int64_t nmax = 0;
+    for (int64_t i = 0; i < nprob; ++i) nmax = std::max(nmax, c.h_off[(size_t)i + 1] - c.h_off[(size_t)i]);
+    // LDS: positions, log-probabilities, counts, one model and orbit per wave; the ToAs and their three constants too
+    // when the largest problem's fit, else they are read from global memory
+    constexpr size_t kLdsCap = 128 * 1024;
+    size_t lds = (w * nd + 2 * w) * sizeof(double) + kTfMcWaves * sizeof(OFWave);
+    const int stage = lds + 6 * (size_t)nmax * sizeof(double) <= kLdsCap;
+    if (stage) lds += 6 * (size_t)nmax * sizeof(double);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_orbit_mcmc), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kLdsCap));
+    const size_t rows = (size_t)nprob * (size_t)steps * w;
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp0 = nullptr, *dlo = nullptr, *dhi = nullptr;
+        const int64_t* doff = nullptr;
+        double *dchain = nullptr, *dlp = nullptr, *dconst = nullptr;
+        int64_t* dacc = nullptr;
+        OFModel* dmod = nullptr;
+        CPModel* dpar = nullptr;
+        TFMap* dmap = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
+        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
+        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
+        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
+        HIPCHK(stage_in(sc, p0, (size_t)nprob * w * nd, dev, &dp0));
+        HIPCHK(stage_in(sc, lo, (size_t)nprob * nd, dev, &dlo));
+        HIPCHK(stage_in(sc, hi, (size_t)nprob * nd, dev, &dhi));
+        HIPCHK(stage_out(sc, chain, rows * nd, dev, &dchain));
+        HIPCHK(stage_out(sc, logprob, rows, dev, &dlp));
+        HIPCHK(stage_out(sc, accepted, (size_t)nprob * w, dev, &dacc));
+        HIPCHK(of_upload(sc, c, ntoa, &dmod, &dpar, &dmap, &dconst));
+        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
+        kt.start();
+        k_orbit_prologue<<<(unsigned)nprob, 256, 0, s>>>(dt, doff, dmod, dpar, (int64_t)ntoa, dconst);
+        HIPCHK(hipGetLastError());
+        k_orbit_mcmc<<<(unsigned)nprob, kTfMcWaves * 64, lds, s>>>(dt, dy, de, dconst, (int64_t)ntoa, doff, dmod, dmap,
+                                                                   dp0, dlo, dhi, (int)W, steps, seed, first_problem,
+                                                                   stage, dchain, dlp, dacc);
         HIPCHK(hipGetLastError());
         kt.stop();
         HIPCHK(copy_back(s, chain, dchain, rows * nd, dev));

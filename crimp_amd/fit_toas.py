@@ -31,8 +31,13 @@ def load_toas_for_fit(tim_file_df: pd.DataFrame, parfile: dict, t_start: float |
     cut to [t_start, t_stop]. The phase is calcphase's (on the device) under ``parfile``: minus the pulse number when
     the model has TRACK -2 and the table a ``pn`` column, else folded into [-0.5, 0.5); then mean-subtracted.
     ``t_mjd_phasewrap`` adds (``mode`` 'add') or removes ('subtract') one cycle from each given MJD on.
-    ValueError for a model with a binary orbit: the fits do not model it."""
+    ValueError for a model with a binary orbit: these fits do not model it (crimp_amd.fit_orbit does)."""
     require_no_binary(parfile)
+    return _load_toas(tim_file_df, parfile, t_start, t_stop, t_mjd_phasewrap, mode)
+
+
+def _load_toas(tim_file_df, parfile, t_start, t_stop, t_mjd_phasewrap, mode):
+    # calcphase evaluates a model with an orbit at the emission time: fit_orbit.load_toas_for_fit comes here directly
     f0 = get_parameter_value(parfile["F0"])
     pt = PulseToAs(tim_file_df)
     pt.time_filter(t_start, t_stop)

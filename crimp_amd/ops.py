@@ -533,6 +533,109 @@ def timing_mcmc(t, y, yerr, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed
     return chain.reshape(nprob, steps, W, nd), logprob.reshape(nprob, steps, W), accepted.reshape(nprob, W)
 
 
+# names a .par gives the orbit fields under: XDOT is A1DOT, E is ECC, TASC takes T0's slot under ELL1
+_ORBIT_ALIASES = {"XDOT": "A1DOT", "E": "ECC", "TASC": "T0"}
+
+
+def orbit_fit_map(keys):
+    """``fit_map`` for a model with an orbit: the keys ``fit_map`` knows, and the orbital keys (PB, A1, T0 | TASC, ECC
+    | E, OM, OMDOT, GAMMA, EPS1, EPS2, PBDOT, A1DOT | XDOT) as FIT_SLOT_BINARY slots. The branch is chosen by the
+    non-orbital keys (none: FIT_WAVES_FIXED)."""
+    if not 1 <= len(keys) <= N.FIT_MAX_DIM:
+        raise ValueError("a fit needs 1..%d free parameters, got %d" % (N.FIT_MAX_DIM, len(keys)))
+    orbital = [_ORBIT_ALIASES.get(k, k) in N.ORBIT_FIELDS for k in keys]
+    spin = [k for k, o in zip(keys, orbital) if not o]
+    sm = fit_map(spin) if spin else None
+    m = N.FitMap()
+    m.ndim = len(keys)
+    m.f0_param = -1
+    m.branch = sm.branch if sm is not None else N.FIT_WAVES_FIXED
+    j = 0
+    for i, (k, o) in enumerate(zip(keys, orbital)):
+        if o:
+            m.slot[i].kind, m.slot[i].index, m.slot[i].sub = (N.FIT_SLOT_BINARY,
+                                                              N.ORBIT_FIELDS.index(_ORBIT_ALIASES.get(k, k)), 0)
+        else:
+            m.slot[i].kind, m.slot[i].index, m.slot[i].sub = sm.slot[j].kind, sm.slot[j].index, sm.slot[j].sub
+            if sm.f0_param == j:
+                m.f0_param = i
+            j += 1
+    return m
+
+
+def _orbit_args(b, t, y, yerr, offsets, pars, fit_bases, wave_bases):
+    if isinstance(pars, N.TimingModel):
+        pars, fit_bases, wave_bases = [pars], [fit_bases], [wave_bases]
+    nprob = len(pars)
+    if len(fit_bases) != nprob or len(wave_bases) != nprob:
+        raise ValueError("one full model, one fit base and one wave base per problem")
+    if offsets is None:
+        n = int(t.numel() if N._is_torch(t) else np.size(t))
+        offsets = np.array([0, n], dtype=np.int64)
+        if N._is_torch(t) and t.is_cuda:
+            import torch
+            offsets = torch.as_tensor(offsets, device=t.device)
+    if int((offsets.numel() if N._is_torch(offsets) else np.size(offsets)) - 1) != nprob:
+        raise ValueError("offsets needs one entry more than there are problems")
+    ptrs = (b.arg(t, np.float64), b.arg(y, np.float64), b.arg(yerr, np.float64), b.arg(offsets, np.int64))
+    ntoa = int(t.numel() if N._is_torch(t) else np.size(t))
+    arr = N.TimingModel * nprob
+    return ptrs, nprob, ntoa, arr(*pars), arr(*fit_bases), arr(*wave_bases)
+
+
+def orbit_nll(t, y, yerr, pars, fit_bases, wave_bases, fmap, pvec, offsets=None, want_mu=False, flags=0):
+    """``timing_nll`` for models with an orbit (crimp_orbit_nll): ``pars`` is the full model of every problem, with its
+    binary block; ``fmap`` an ``orbit_fit_map``. A vector whose corrected orbit is outside the limits gives +inf."""
+    L = N.load()
+    b = N.Buffers()
+    (tp, yp, ep, op), nprob, ntoa, pm, fb, wb = _orbit_args(b, t, y, yerr, offsets, pars, fit_bases, wave_bases)
+    nd = int(fmap.ndim)
+    tot = int(pvec.numel() if N._is_torch(pvec) else np.size(pvec))
+    if nd < 1 or tot == 0 or tot % (nprob * nd):
+        raise ValueError("pvec must be [nprob, P, ndim]")
+    P = tot // (nprob * nd)
+    pp = b.arg(pvec, np.float64)
+    nll = _empty_like_input(t, nprob * P, b)
+    mu = _empty_like_input(t, P * ntoa, b) if want_mu else None
+    nllp = b.arg(nll, np.float64, writable=True)
+    mup = b.arg(mu, np.float64, writable=True) if want_mu else None
+    with b.device_guard():
+        N.check(L.crimp_orbit_nll(tp, yp, ep, op, nprob, pm, fb, wb, ctypes.byref(fmap), pp, P, nllp, mup,
+                                  b.flags(flags), b.stream()))
+    nll = nll.reshape(nprob, P)
+    return (nll, mu) if want_mu else nll
+
+
+def orbit_mcmc(t, y, yerr, pars, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets=None, first_problem=0,
+               flags=0):
+    """``timing_mcmc`` for models with an orbit (crimp_orbit_mcmc); the arguments of ``orbit_nll`` and ``timing_mcmc``,
+    the same outputs."""
+    L = N.load()
+    b = N.Buffers()
+    (tp, yp, ep, op), nprob, ntoa, pm, fb, wb = _orbit_args(b, t, y, yerr, offsets, pars, fit_bases, wave_bases)
+    nd = int(fmap.ndim)
+    shape = tuple(p0.shape)
+    if len(shape) != 3 or shape[0] != nprob or shape[2] != nd:
+        raise ValueError("p0 must be [nprob, W, ndim]")
+    W, steps = int(shape[1]), int(steps)
+    for a in (lo, hi):
+        if int(a.numel() if N._is_torch(a) else np.size(a)) != nprob * nd:
+            raise ValueError("lo and hi must be [nprob, ndim]")
+    pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
+    rows = nprob * max(steps, 0) * W
+    chain = _empty_like_input(t, rows * nd, b)
+    logprob = _empty_like_input(t, rows, b)
+    accepted = _empty_like_input(t, nprob * W, b, dtype=np.int64)
+    cp = b.arg(chain, np.float64, writable=True)
+    lpp = b.arg(logprob, np.float64, writable=True)
+    ap = b.arg(accepted, np.int64, writable=True)
+    with b.device_guard():
+        N.check(L.crimp_orbit_mcmc(tp, yp, ep, op, nprob, pm, fb, wb, ctypes.byref(fmap), pp, lop, hip_, W, steps,
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_problem), cp, lpp, ap, b.flags(flags),
+                                   b.stream()))
+    return chain.reshape(nprob, steps, W, nd), logprob.reshape(nprob, steps, W), accepted.reshape(nprob, W)
+
+
 def _photon_args(b, t, x, par, phoff):
     n = int(t.numel() if N._is_torch(t) else np.size(t))
     if int(x.numel() if N._is_torch(x) else np.size(x)) != n:

@@ -374,6 +374,59 @@ int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, 
                       int64_t steps, uint64_t seed, int64_t first_problem, double* chain, double* logprob,
                       int64_t* accepted, uint32_t flags, void* stream);
 
+/* Timing-model fits of ToAs under a binary orbit, the orbital keys free (not in the reference; csrc/orbit_fit.h,
+ * DESIGN.md 5.9). crimp_timing_nll / _mcmc refuse a model with an orbit and a CRIMP_FIT_SLOT_BINARY slot; these two
+ * calls are the same fits with par[i], the full model of problem i with its binary block, beside the two bases (whose
+ * own binary blocks are not read).
+ *
+ * A CRIMP_FIT_SLOT_BINARY slot (index = CRIMP_ORBIT_*, sub not read) corrects a field of par's orbit as
+ * inject_free_params corrects every ordinary key: field(p) = par's field - p, in the unit of crimp_timing_model's
+ * binary block (days, light-seconds, MJD, degrees, degrees / yr; PBDOT and A1DOT dimensionless), the fp64 difference.
+ * With B0 the orbit of par, B(p) the corrected one, tau_B(t) the delay crimp_binary_delay defines and phi_M(t') the
+ * spin phase of model M at the emission time t', the model residual of ToA i before the mean is subtracted is
+ *   m_i(p) = phi_fit(p)(teF_i) + R_i(p),   R_i(p) = phi_par(te0_i) - phi_par(teF_i),
+ *   te0 = t - tau_B0(t) / 86400,   teF = t - tau_B(p)(t) / 86400,
+ * phi_fit(p) the fit model of crimp_timing_nll (same branches, F0_base - dF0 and wave_base), evaluated at the emission
+ * time of the corrected orbit. R is evaluated as one small phase, dtau (nu - nud dtau / 2) with dtau = tau_B(p) -
+ * tau_B0 and nu, nud the first two derivatives of phi_par at te0 (glitches active there and waves included), computed
+ * once per call; the dropped term is |phi_par'''| |dtau|^3 / 6. A ToA with a glitch epoch of par between te0 and teF
+ * is outside the contract. mu = m - mean(m); NLL = gaussian_nll(y - mean(y), mu, yerr). With no BINARY slot, or with
+ * every orbital entry 0, R is exactly 0: the spin fit under the fixed orbit.
+ * A vector whose corrected orbit is outside the limits of crimp_binary_delay (a non-finite field included) is
+ * inadmissible: NLL = +inf, its mu row +inf, and the sampler rejects it without evaluating it, as it rejects a
+ * proposal outside the box.
+ * CRIMP_ERR_ARG of both calls, nothing written: the texts of crimp_timing_nll / _mcmc; "the model has no binary";
+ * a base orbit outside the limits (the texts of crimp_binary_delay); "slot names an orbit field the model's kind does
+ * not have" (ECC, OM, OMDOT, GAMMA under ELL1; EPS1, EPS2 under BT); "slot names an orbit field outside
+ * CRIMP_ORBIT_PB..CRIMP_ORBIT_A1DOT"; "two slots name one orbit field". */
+#define CRIMP_FIT_SLOT_BINARY 3 /* index = CRIMP_ORBIT_* (crimp_orbit_nll / _mcmc only) */
+#define CRIMP_ORBIT_PB 0
+#define CRIMP_ORBIT_A1 1
+#define CRIMP_ORBIT_T0 2 /* T0 (BT) or TASC (ELL1) */
+#define CRIMP_ORBIT_ECC 3
+#define CRIMP_ORBIT_OM 4
+#define CRIMP_ORBIT_OMDOT 5
+#define CRIMP_ORBIT_GAMMA 6
+#define CRIMP_ORBIT_EPS1 7
+#define CRIMP_ORBIT_EPS2 8
+#define CRIMP_ORBIT_PBDOT 9
+#define CRIMP_ORBIT_A1DOT 10
+
+/* crimp_timing_nll with par[nprob]: the same arrays, outputs and independence of the launch shape. */
+int crimp_orbit_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets, int64_t nprob,
+                    const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                    const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec, int64_t P,
+                    double* nll, double* mu, uint32_t flags, void* stream);
+
+/* crimp_timing_mcmc with par[nprob]: the same move, halves, Philox counters, first_problem and outputs; logprob equals
+ * -crimp_orbit_nll(chain) bit for bit, and no inadmissible vector enters a chain. */
+int crimp_orbit_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets, int64_t nprob,
+                     const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                     const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
+                     const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                     int64_t first_problem, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
+                     void* stream);
+
 /* Photon-domain timing fits (not in the reference; csrc/photon_fit.h).
  *
  * The vector p corrects the model as inject_free_params does, full(p) = par - p on every free key, and its likelihood
