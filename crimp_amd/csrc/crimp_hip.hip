@@ -21,6 +21,7 @@
 #include <mutex>
 #include <string>
 #include <chrono>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/crimp_hip.h"
@@ -1646,6 +1647,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "toa_fit.h"
 #include "toa_shape.h"
 #include "phase_cube.h"
+#include "stretch_move.h"
 #include "timing_fit.h"
 #include "orbit_fit.h"
 #include "sim_events.h"
@@ -3299,136 +3301,30 @@ static int tf_host_offsets(const Call& c, const int64_t* offsets, int64_t nprob,
     return CRIMP_OK;
 }
 
-extern "C" int crimp_timing_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
-                                int64_t nprob, const crimp_timing_model* fit_base,
-                                const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec,
-                                int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
-    ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && pvec != nullptr && nll != nullptr, "null argument");
-    ARGCHK(P >= 1 && P <= (int64_t(1) << 24), "P out of range");
-    const Call call(flags, stream);
-    const bool dev = call.dev;
-    hipStream_t s = call.s;
+// What a ToA-fit call holds after its host checks, binary-free (TimingLik) or under an orbit (OrbitLik): the offsets,
+// the problems' models in the kernels' form, the map and (the orbit's calls) the par spin models of the prologue
+template <class Lik>
+struct FitCall {
     std::vector<int64_t> h_off;
-    std::vector<TFModel> models;
-    TFMap dm;
-    int rc = tf_host_offsets(call, offsets, nprob, &h_off);
-    if (rc != CRIMP_OK) return rc;
-    rc = tf_prepare(h_off.data(), nprob, fit_base, wave_base, map, &models, &dm);
-    if (rc != CRIMP_OK) return rc;
-    const int64_t groups = cdiv(P, kTfNllWaves);
-    ARGCHK(nprob * groups <= (int64_t(1) << 30), "too many parameter vectors for one launch");
-    const size_t ntoa = (size_t)h_off[(size_t)nprob], nd = (size_t)dm.ndim;
-    {
-        Scratch sc(s);
-        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp = nullptr;
-        const int64_t* doff = nullptr;
-        double *dnll = nullptr, *dmu = nullptr;
-        TFModel* dmod = nullptr;
-        TFMap* dmap = nullptr;
-        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
-        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
-        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
-        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
-        HIPCHK(stage_in(sc, pvec, (size_t)nprob * (size_t)P * nd, dev, &dp));
-        HIPCHK(stage_out(sc, nll, (size_t)nprob * (size_t)P, dev, &dnll));
-        HIPCHK(stage_out(sc, mu, (size_t)P * ntoa, dev, &dmu));
-        HIPCHK(sc.alloc(&dmod, models.size()));
-        HIPCHK(sc.alloc(&dmap, 1));
-        HIPCHK(h2d(dmod, models.data(), models.size() * sizeof(TFModel)));
-        HIPCHK(h2d(dmap, &dm, sizeof(TFMap)));
-        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
-        kt.start();
-        k_timing_nll<<<(unsigned)(nprob * groups), kTfNllWaves * 64, 0, s>>>(dt, dy, de, doff, dmod, dmap, dp, P, groups,
-                                                                             dnll, dmu);
-        HIPCHK(hipGetLastError());
-        kt.stop();
-        HIPCHK(copy_back(s, nll, dnll, (size_t)nprob * (size_t)P, dev));
-        HIPCHK(copy_back(s, mu, dmu, (size_t)P * ntoa, dev));
-    }
-    return finish(s, flags);
-}
-
-extern "C" int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
-                                 int64_t nprob, const crimp_timing_model* fit_base,
-                                 const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
-                                 const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
-                                 int64_t first_problem, double* chain, double* logprob, int64_t* accepted,
-                                 uint32_t flags, void* stream) {
-    ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && p0 != nullptr && lo != nullptr && hi != nullptr &&
-               chain != nullptr && logprob != nullptr && accepted != nullptr, "null argument");
-    ARGCHK(map != nullptr && map->ndim >= 1 && map->ndim <= CRIMP_FIT_MAX_DIM, "ndim must be 1..CRIMP_FIT_MAX_DIM");
-    ARGCHK(W >= 2 && W % 2 == 0 && W <= 256 && W >= 2 * map->ndim, "walkers: even, >= 2 ndim and <= 256");
-    ARGCHK(steps >= 1 && steps <= (int64_t(1) << 31), "steps out of range");
-    ARGCHK(first_problem >= 0 && first_problem + nprob <= (int64_t(1) << 32), "first_problem out of range");
-    const Call call(flags, stream);
-    const bool dev = call.dev;
-    hipStream_t s = call.s;
-    std::vector<int64_t> h_off;
-    std::vector<TFModel> models;
-    TFMap dm;
-    int rc = tf_host_offsets(call, offsets, nprob, &h_off);
-    if (rc != CRIMP_OK) return rc;
-    rc = tf_prepare(h_off.data(), nprob, fit_base, wave_base, map, &models, &dm);
-    if (rc != CRIMP_OK) return rc;
-    const size_t ntoa = (size_t)h_off[(size_t)nprob], nd = (size_t)dm.ndim, w = (size_t)W;
-    int64_t nmax = 0;
-    for (int64_t i = 0; i < nprob; ++i) nmax = std::max(nmax, h_off[(size_t)i + 1] - h_off[(size_t)i]);
-    // LDS: positions, log-probabilities, counts, one model per wave; the ToAs too when the largest problem's fit
-    constexpr size_t kLdsCap = 128 * 1024;
-    size_t lds = (w * nd + 2 * w) * sizeof(double) + kTfMcWaves * sizeof(CPModel);
-    const int stage = lds + 3 * (size_t)nmax * sizeof(double) <= kLdsCap;
-    if (stage) lds += 3 * (size_t)nmax * sizeof(double);
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_timing_mcmc), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kLdsCap));
-    const size_t rows = (size_t)nprob * (size_t)steps * w;
-    {
-        Scratch sc(s);
-        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp0 = nullptr, *dlo = nullptr, *dhi = nullptr;
-        const int64_t* doff = nullptr;
-        double *dchain = nullptr, *dlp = nullptr;
-        int64_t* dacc = nullptr;
-        TFModel* dmod = nullptr;
-        TFMap* dmap = nullptr;
-        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
-        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
-        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
-        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
-        HIPCHK(stage_in(sc, p0, (size_t)nprob * w * nd, dev, &dp0));
-        HIPCHK(stage_in(sc, lo, (size_t)nprob * nd, dev, &dlo));
-        HIPCHK(stage_in(sc, hi, (size_t)nprob * nd, dev, &dhi));
-        HIPCHK(stage_out(sc, chain, rows * nd, dev, &dchain));
-        HIPCHK(stage_out(sc, logprob, rows, dev, &dlp));
-        HIPCHK(stage_out(sc, accepted, (size_t)nprob * w, dev, &dacc));
-        HIPCHK(sc.alloc(&dmod, models.size()));
-        HIPCHK(sc.alloc(&dmap, 1));
-        HIPCHK(h2d(dmod, models.data(), models.size() * sizeof(TFModel)));
-        HIPCHK(h2d(dmap, &dm, sizeof(TFMap)));
-        KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
-        kt.start();
-        k_timing_mcmc<<<(unsigned)nprob, kTfMcWaves * 64, lds, s>>>(dt, dy, de, doff, dmod, dmap, dp0, dlo, dhi, (int)W,
-                                                                    steps, seed, first_problem, stage, dchain, dlp, dacc);
-        HIPCHK(hipGetLastError());
-        kt.stop();
-        HIPCHK(copy_back(s, chain, dchain, rows * nd, dev));
-        HIPCHK(copy_back(s, logprob, dlp, rows, dev));
-        HIPCHK(copy_back(s, accepted, dacc, (size_t)nprob * w, dev));
-    }
-    return finish(s, flags);
-}
-
-// ---- timing-model fits of ToAs under a binary orbit (orbit_fit.h)
-// What both calls hold after their host checks: the offsets, the problems' models in the kernels' form, the par spin
-// models of the prologue and the map
-struct OFCall {
-    std::vector<int64_t> h_off;
-    std::vector<OFModel> models;
+    std::vector<typename Lik::Base> models;
     std::vector<CPModel> parm;
     TFMap dm;
 };
+template <class Lik>
+constexpr bool kFitOrbit = std::is_same<Lik, OrbitLik>::value;
 
-static int of_prepare(const Call& call, const int64_t* offsets, int64_t nprob, const crimp_timing_model* par,
-                      const crimp_timing_model* fit_base, const crimp_timing_model* wave_base,
-                      const crimp_fit_map* map, OFCall* c) {
+static int fit_prepare(const Call& call, const int64_t* offsets, int64_t nprob, const crimp_timing_model*,
+                       const crimp_timing_model* fit_base, const crimp_timing_model* wave_base,
+                       const crimp_fit_map* map, FitCall<TimingLik>* c) {
+    const int rc = tf_host_offsets(call, offsets, nprob, &c->h_off);
+    if (rc != CRIMP_OK) return rc;
+    return tf_prepare(c->h_off.data(), nprob, fit_base, wave_base, map, &c->models, &c->dm);
+}
+
+// the orbit's calls: par is required (checked before the offsets are read), BINARY slots are admitted
+static int fit_prepare(const Call& call, const int64_t* offsets, int64_t nprob, const crimp_timing_model* par,
+                       const crimp_timing_model* fit_base, const crimp_timing_model* wave_base,
+                       const crimp_fit_map* map, FitCall<OrbitLik>* c) {
     ARGCHK(par != nullptr, "null argument");
     int rc = tf_host_offsets(call, offsets, nprob, &c->h_off);
     if (rc != CRIMP_OK) return rc;
@@ -3471,57 +3367,77 @@ static int of_prepare(const Call& call, const int64_t* offsets, int64_t nprob, c
     return CRIMP_OK;
 }
 
-// the device copies of an OFCall and the room of the per-ToA constants
-static hipError_t of_upload(Scratch& sc, const OFCall& c, size_t ntoa, OFModel** dmod, CPModel** dparp, TFMap** dmap,
-                            double** dconst) {
-    CPModel*& dpar = *dparp;
+// The device side of a call: the arrays of all problems as the kernels take them, the offsets, the models and the map
+template <class Lik>
+struct FitDev {
+    typename Lik::Data d{};
+    const int64_t* off = nullptr;
+    typename Lik::Base* mod = nullptr;
+    TFMap* map = nullptr;
+    CPModel* par = nullptr;  // the orbit's calls: the prologue's models, and the constants it writes
+    double* consts = nullptr;
+};
+
+// the device copies of a FitCall; for the orbit also the room of the per-ToA constants, the arrays d.a[3..5]
+template <class Lik>
+static hipError_t fit_upload(Scratch& sc, const FitCall<Lik>& c, size_t ntoa, FitDev<Lik>* D) {
     hipError_t e;
-    if ((e = sc.alloc(dmod, c.models.size())) != hipSuccess) return e;
-    if ((e = sc.alloc(&dpar, c.parm.size())) != hipSuccess) return e;
-    if ((e = sc.alloc(dmap, 1)) != hipSuccess) return e;
-    if ((e = sc.alloc(dconst, 3 * ntoa)) != hipSuccess) return e;
-    if ((e = h2d(*dmod, c.models.data(), c.models.size() * sizeof(OFModel))) != hipSuccess) return e;
-    if ((e = h2d(dpar, c.parm.data(), c.parm.size() * sizeof(CPModel))) != hipSuccess) return e;
-    return h2d(*dmap, &c.dm, sizeof(TFMap));
+    if ((e = sc.alloc(&D->mod, c.models.size())) != hipSuccess) return e;
+    if ((e = sc.alloc(&D->map, 1)) != hipSuccess) return e;
+    if ((e = h2d(D->mod, c.models.data(), c.models.size() * sizeof(typename Lik::Base))) != hipSuccess) return e;
+    if ((e = h2d(D->map, &c.dm, sizeof(TFMap))) != hipSuccess) return e;
+    if constexpr (kFitOrbit<Lik>) {
+        if ((e = sc.alloc(&D->par, c.parm.size())) != hipSuccess) return e;
+        if ((e = sc.alloc(&D->consts, 3 * ntoa)) != hipSuccess) return e;
+        if ((e = h2d(D->par, c.parm.data(), c.parm.size() * sizeof(CPModel))) != hipSuccess) return e;
+        for (int k = 0; k < 3; ++k) D->d.a[3 + k] = D->consts + (size_t)k * ntoa;
+    }
+    return hipSuccess;
 }
 
-extern "C" int crimp_orbit_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
-                               int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
-                               const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec,
-                               int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
+// the launches before a call's kernel: the orbit's per-ToA constants (part of a call's timed cost)
+template <class Lik>
+static hipError_t fit_prologue(hipStream_t s, int64_t nprob, size_t ntoa, const FitDev<Lik>& D) {
+    if constexpr (kFitOrbit<Lik>)
+        k_orbit_prologue<<<(unsigned)nprob, 256, 0, s>>>(D.d.a[0], D.off, D.mod, D.par, (int64_t)ntoa, D.consts);
+    return hipGetLastError();
+}
+
+// crimp_timing_nll and crimp_orbit_nll (par: the orbit's call alone)
+template <class Lik>
+static int fit_nll_call(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                        int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                        const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec, int64_t P,
+                        double* nll, double* mu, uint32_t flags, void* stream) {
     ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && pvec != nullptr && nll != nullptr, "null argument");
     ARGCHK(P >= 1 && P <= (int64_t(1) << 24), "P out of range");
     const Call call(flags, stream);
     const bool dev = call.dev;
     hipStream_t s = call.s;
-    OFCall c;
-    const int rc = of_prepare(call, offsets, nprob, par, fit_base, wave_base, map, &c);
+    FitCall<Lik> c;
+    const int rc = fit_prepare(call, offsets, nprob, par, fit_base, wave_base, map, &c);
     if (rc != CRIMP_OK) return rc;
     const int64_t groups = cdiv(P, kTfNllWaves);
     ARGCHK(nprob * groups <= (int64_t(1) << 30), "too many parameter vectors for one launch");
     const size_t ntoa = (size_t)c.h_off[(size_t)nprob], nd = (size_t)c.dm.ndim;
     {
         Scratch sc(s);
-        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp = nullptr;
-        const int64_t* doff = nullptr;
-        double *dnll = nullptr, *dmu = nullptr, *dconst = nullptr;
-        OFModel* dmod = nullptr;
-        CPModel* dpar = nullptr;
-        TFMap* dmap = nullptr;
-        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
-        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
-        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
-        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
+        FitDev<Lik> D;
+        const double* dp = nullptr;
+        double *dnll = nullptr, *dmu = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &D.d.a[0]));
+        HIPCHK(stage_in(sc, y, ntoa, dev, &D.d.a[1]));
+        HIPCHK(stage_in(sc, yerr, ntoa, dev, &D.d.a[2]));
+        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &D.off));
         HIPCHK(stage_in(sc, pvec, (size_t)nprob * (size_t)P * nd, dev, &dp));
         HIPCHK(stage_out(sc, nll, (size_t)nprob * (size_t)P, dev, &dnll));
         HIPCHK(stage_out(sc, mu, (size_t)P * ntoa, dev, &dmu));
-        HIPCHK(of_upload(sc, c, ntoa, &dmod, &dpar, &dmap, &dconst));
+        HIPCHK(fit_upload(sc, c, ntoa, &D));
         KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
-        kt.start();  // the prologue is part of a call's cost
-        k_orbit_prologue<<<(unsigned)nprob, 256, 0, s>>>(dt, doff, dmod, dpar, (int64_t)ntoa, dconst);
-        HIPCHK(hipGetLastError());
-        k_orbit_nll<<<(unsigned)(nprob * groups), kTfNllWaves * 64, 0, s>>>(dt, dy, de, dconst, (int64_t)ntoa, doff, dmod,
-                                                                            dmap, dp, P, groups, dnll, dmu);
+        kt.start();
+        HIPCHK(fit_prologue(s, nprob, ntoa, D));
+        k_fit_nll<Lik><<<(unsigned)(nprob * groups), kTfNllWaves * 64, 0, s>>>(D.d, D.off, D.mod, D.map, dp, P, groups,
+                                                                               dnll, dmu);
         HIPCHK(hipGetLastError());
         kt.stop();
         HIPCHK(copy_back(s, nll, dnll, (size_t)nprob * (size_t)P, dev));
@@ -3530,12 +3446,14 @@ extern "C" int crimp_orbit_nll(const double* t_mjd, const double* y, const doubl
     return finish(s, flags);
 }
 
-extern "C" int crimp_orbit_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
-                                int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
-                                const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
-                                const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
-                                int64_t first_problem, double* chain, double* logprob, int64_t* accepted,
-                                uint32_t flags, void* stream) {
+// crimp_timing_mcmc and crimp_orbit_mcmc (par: the orbit's call alone)
+template <class Lik>
+static int fit_mcmc_call(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                         int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                         const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
+                         const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                         int64_t first_problem, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
+                         void* stream) {
     ARGCHK(t_mjd != nullptr && y != nullptr && yerr != nullptr && p0 != nullptr && lo != nullptr && hi != nullptr &&
                chain != nullptr && logprob != nullptr && accepted != nullptr, "null argument");
     ARGCHK(map != nullptr && map->ndim >= 1 && map->ndim <= CRIMP_FIT_MAX_DIM, "ndim must be 1..CRIMP_FIT_MAX_DIM");
@@ -3545,48 +3463,44 @@ extern "C" int crimp_orbit_mcmc(const double* t_mjd, const double* y, const doub
     const Call call(flags, stream);
     const bool dev = call.dev;
     hipStream_t s = call.s;
-    OFCall c;
-    const int rc = of_prepare(call, offsets, nprob, par, fit_base, wave_base, map, &c);
+    FitCall<Lik> c;
+    const int rc = fit_prepare(call, offsets, nprob, par, fit_base, wave_base, map, &c);
     if (rc != CRIMP_OK) return rc;
     const size_t ntoa = (size_t)c.h_off[(size_t)nprob], nd = (size_t)c.dm.ndim, w = (size_t)W;
     int64_t nmax = 0;
     for (int64_t i = 0; i < nprob; ++i) nmax = std::max(nmax, c.h_off[(size_t)i + 1] - c.h_off[(size_t)i]);
-    // LDS: positions, log-probabilities, counts, one model and orbit per wave; the ToAs and their three constants too
-    // when the largest problem's fit, else they are read from global memory
+    // LDS: positions, log-probabilities, counts, one Lik::Wave per wave; the per-ToA arrays too when the largest
+    // problem's fit, else they are read from global memory
     constexpr size_t kLdsCap = 128 * 1024;
-    size_t lds = (w * nd + 2 * w) * sizeof(double) + kTfMcWaves * sizeof(OFWave);
-    const int stage = lds + 6 * (size_t)nmax * sizeof(double) <= kLdsCap;
-    if (stage) lds += 6 * (size_t)nmax * sizeof(double);
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_orbit_mcmc), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kLdsCap));
+    size_t lds = (w * nd + 2 * w) * sizeof(double) + kTfMcWaves * sizeof(typename Lik::Wave);
+    const int stage = lds + Lik::kArrays * (size_t)nmax * sizeof(double) <= kLdsCap;
+    if (stage) lds += Lik::kArrays * (size_t)nmax * sizeof(double);
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fit_mcmc<Lik>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsCap));
     const size_t rows = (size_t)nprob * (size_t)steps * w;
     {
         Scratch sc(s);
-        const double *dt = nullptr, *dy = nullptr, *de = nullptr, *dp0 = nullptr, *dlo = nullptr, *dhi = nullptr;
-        const int64_t* doff = nullptr;
-        double *dchain = nullptr, *dlp = nullptr, *dconst = nullptr;
+        FitDev<Lik> D;
+        const double *dp0 = nullptr, *dlo = nullptr, *dhi = nullptr;
+        double *dchain = nullptr, *dlp = nullptr;
         int64_t* dacc = nullptr;
-        OFModel* dmod = nullptr;
-        CPModel* dpar = nullptr;
-        TFMap* dmap = nullptr;
-        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &dt));
-        HIPCHK(stage_in(sc, y, ntoa, dev, &dy));
-        HIPCHK(stage_in(sc, yerr, ntoa, dev, &de));
-        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &doff));
+        HIPCHK(stage_in(sc, t_mjd, ntoa, dev, &D.d.a[0]));
+        HIPCHK(stage_in(sc, y, ntoa, dev, &D.d.a[1]));
+        HIPCHK(stage_in(sc, yerr, ntoa, dev, &D.d.a[2]));
+        HIPCHK(stage_in(sc, offsets, (size_t)nprob + 1, dev, &D.off));
         HIPCHK(stage_in(sc, p0, (size_t)nprob * w * nd, dev, &dp0));
         HIPCHK(stage_in(sc, lo, (size_t)nprob * nd, dev, &dlo));
         HIPCHK(stage_in(sc, hi, (size_t)nprob * nd, dev, &dhi));
         HIPCHK(stage_out(sc, chain, rows * nd, dev, &dchain));
         HIPCHK(stage_out(sc, logprob, rows, dev, &dlp));
         HIPCHK(stage_out(sc, accepted, (size_t)nprob * w, dev, &dacc));
-        HIPCHK(of_upload(sc, c, ntoa, &dmod, &dpar, &dmap, &dconst));
+        HIPCHK(fit_upload(sc, c, ntoa, &D));
         KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
         kt.start();
-        k_orbit_prologue<<<(unsigned)nprob, 256, 0, s>>>(dt, doff, dmod, dpar, (int64_t)ntoa, dconst);
-        HIPCHK(hipGetLastError());
-        k_orbit_mcmc<<<(unsigned)nprob, kTfMcWaves * 64, lds, s>>>(dt, dy, de, dconst, (int64_t)ntoa, doff, dmod, dmap,
-                                                                   dp0, dlo, dhi, (int)W, steps, seed, first_problem,
-                                                                   stage, dchain, dlp, dacc);
+        HIPCHK(fit_prologue(s, nprob, ntoa, D));
+        k_fit_mcmc<Lik><<<(unsigned)nprob, kTfMcWaves * 64, lds, s>>>(D.d, D.off, D.mod, D.map, dp0, dlo, dhi, (int)W,
+                                                                      steps, seed, first_problem, stage, dchain, dlp,
+                                                                      dacc);
         HIPCHK(hipGetLastError());
         kt.stop();
         HIPCHK(copy_back(s, chain, dchain, rows * nd, dev));
@@ -3594,6 +3508,42 @@ extern "C" int crimp_orbit_mcmc(const double* t_mjd, const double* y, const doub
         HIPCHK(copy_back(s, accepted, dacc, (size_t)nprob * w, dev));
     }
     return finish(s, flags);
+}
+
+extern "C" int crimp_timing_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                                int64_t nprob, const crimp_timing_model* fit_base,
+                                const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec,
+                                int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
+    return fit_nll_call<TimingLik>(t_mjd, y, yerr, offsets, nprob, nullptr, fit_base, wave_base, map, pvec, P, nll, mu,
+                                   flags, stream);
+}
+
+extern "C" int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                                 int64_t nprob, const crimp_timing_model* fit_base,
+                                 const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
+                                 const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                                 int64_t first_problem, double* chain, double* logprob, int64_t* accepted,
+                                 uint32_t flags, void* stream) {
+    return fit_mcmc_call<TimingLik>(t_mjd, y, yerr, offsets, nprob, nullptr, fit_base, wave_base, map, p0, lo, hi, W,
+                                    steps, seed, first_problem, chain, logprob, accepted, flags, stream);
+}
+
+extern "C" int crimp_orbit_nll(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                               int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                               const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* pvec,
+                               int64_t P, double* nll, double* mu, uint32_t flags, void* stream) {
+    return fit_nll_call<OrbitLik>(t_mjd, y, yerr, offsets, nprob, par, fit_base, wave_base, map, pvec, P, nll, mu,
+                                  flags, stream);
+}
+
+extern "C" int crimp_orbit_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
+                                int64_t nprob, const crimp_timing_model* par, const crimp_timing_model* fit_base,
+                                const crimp_timing_model* wave_base, const crimp_fit_map* map, const double* p0,
+                                const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
+                                int64_t first_problem, double* chain, double* logprob, int64_t* accepted,
+                                uint32_t flags, void* stream) {
+    return fit_mcmc_call<OrbitLik>(t_mjd, y, yerr, offsets, nprob, par, fit_base, wave_base, map, p0, lo, hi, W, steps,
+                                   seed, first_problem, chain, logprob, accepted, flags, stream);
 }
 
 // ---- photon-domain timing fits (photon_fit.h)

@@ -1,7 +1,8 @@
 // orbit_fit.h -- timing-model fits of ToAs under a binary orbit (BT, ELL1) with the orbital keys free: the batched
 // Gaussian NLL and the ensemble MCMC that samples it. Not in the reference; the definition is DESIGN.md 5.9. Included by
-// crimp_hip.hip after timing_fit.h, whose layout, summation order, move and Philox counters it keeps; the C-ABI
-// (crimp_orbit_nll, crimp_orbit_mcmc) is in its section 6. k_timing_nll / k_timing_mcmc are not touched.
+// crimp_hip.hip after timing_fit.h: this header holds OrbitLik, the policy with which timing_fit.h's k_fit_nll and
+// k_fit_mcmc (layout, summation order, move and Philox counters) fit the orbit, and k_orbit_prologue; the C-ABI
+// (crimp_orbit_nll, crimp_orbit_mcmc) is in crimp_hip.hip's section 6.
 //
 // A problem is a set of ToAs with the full model par (its orbit B0 included) and the fit-model base of timing_fit.h. A
 // parameter vector p overwrites the fit model's fields as there, and its CRIMP_FIT_SLOT_BINARY entries correct the
@@ -22,9 +23,9 @@ constexpr int kOfFields = 11;  // CRIMP_ORBIT_PB .. CRIMP_ORBIT_A1DOT
 #ifndef CRIMP_OF_KEEP
 #define CRIMP_OF_KEEP 4
 #endif
-// first-pass phases a lane keeps in registers: ToAs below 64 * kOfKeep are evaluated once (0: every ToA twice, as
-// tf_nll). 4 against 0 at P = 4096 x 84 ToAs: 62.7 -> 43.0 us (BT, e = 0.7), 44.8 -> 33.8 us (ELL1)
-// (profiles/orbit_fit_ab_keep.log); the values do not change, the summation order is the same.
+// first-pass phases a lane keeps in registers (fit_nll's kKeep): ToAs below 64 * kOfKeep are evaluated once (0: every
+// ToA twice, as the binary-free fit). 4 against 0 at P = 4096 x 84 ToAs: 62.7 -> 43.0 us (BT, e = 0.7), 44.8 -> 33.8
+// us (ELL1) (profiles/orbit_fit_ab_keep.log); the values do not change, the summation order is the same.
 constexpr int kOfKeep = CRIMP_OF_KEEP;
 
 struct OFOrbit {
@@ -90,28 +91,12 @@ __device__ __forceinline__ void of_load(OFWave* Wv, const OFModel* __restrict__ 
     tf_load_model(&Wv->m, &base->tf, lane);
 }
 
-// parameter k (lane k's v) into the field its slot names (tf_apply's three kinds; a BINARY slot: base - v into the raw
-// orbit), then the orbit of the raw fields. False (in every lane) for an orbit outside the limits.
+// parameter k (lane k's v) into the field its slot names (tf_apply_slots; a BINARY slot: base - v into the raw orbit),
+// then the orbit of the raw fields. False (in every lane) for an orbit outside the limits.
 __device__ __forceinline__ bool of_apply(OFWave* Wv, const OFModel* __restrict__ base, const TFMap* __restrict__ map,
                                          double v, int lane) {
 #pragma clang fp contract(off)
-    CPModel* M = &Wv->m;
-    const int nd = map->ndim;
-    const int fp = map->f0_param;
-    const double df0 = __shfl(v, fp >= 0 ? fp : 0);
-    if (lane < nd) {
-        const int kind = map->kind[lane], a = map->a[lane], b = map->b[lane];
-        if (kind == CRIMP_FIT_SLOT_F)
-            M->coef[a] = map->inv_fact[a] * v;
-        else if (kind == CRIMP_FIT_SLOT_GLITCH)
-            M->glitch[a][b] = v;
-        else if (kind == CRIMP_FIT_SLOT_WAVE)
-            M->wave_ab[a][b] = v;
-        else
-            Wv->raw[a] = base->ob.raw[a] - v;
-    }
-    if (lane == 0) M->f0 = base->tf.f0_base - (fp >= 0 ? df0 : 0.0);
-    tf_wave_sync();
+    tf_apply_slots<true>(&Wv->m, base->tf.f0_base, map, v, lane, Wv->raw, base->ob.raw);
     const bool ok = of_derive(base->ob.kind, Wv->raw, &Wv->b, lane == 0);
     tf_wave_sync();
     return ok;
@@ -187,7 +172,7 @@ __global__ __launch_bounds__(256) void k_orbit_prologue(const double* __restrict
 
 // a problem's ToAs and their constants
 struct OFData {
-    const double *t, *y, *e, *tau0, *nu, *nud;
+    const double* a[6];  // t, y, yerr, tau0, nu, nud
 };
 
 __device__ __noinline__ double of_phase(const OFWave* Wv, double t, double tau0, double nu, double nud) {
@@ -198,172 +183,22 @@ __device__ __noinline__ double of_phase(const OFWave* Wv, double t, double tau0,
     return cp_one_t<true>(&Wv->m, t, tau) + R;
 }
 
-// tf_nll on of_phase (all lanes of one wave; the value is returned in every lane). The summation order is tf_nll's.
-// The phases of the first 64 * kOfKeep ToAs stay in registers between the mean's pass and the residuals' pass; past
-// them a ToA is evaluated twice, as tf_nll does.
-__device__ __noinline__ double of_nll(const OFWave* Wv, const OFData d, int n, double* mu_out, int lane) {
-#pragma clang fp contract(off)
-    double sp = 0.0, sy = 0.0;
-    double keep[kOfKeep > 0 ? kOfKeep : 1];
-#pragma unroll
-    for (int k = 0; k < kOfKeep; ++k) {
-        const int i = lane + 64 * k;
-        keep[k] = 0.0;
-        if (i < n) {
-            keep[k] = of_phase(Wv, d.t[i], d.tau0[i], d.nu[i], d.nud[i]);
-            sp += keep[k];
-            sy += d.y[i];
-        }
+// the orbit fit as k_fit_nll / k_fit_mcmc see it. A vector whose orbit is outside the limits is refused: NLL = +inf,
+// its mu row +inf, and the sampler does not evaluate it.
+struct OrbitLik {
+    using Wave = OFWave;
+    using Base = OFModel;
+    using Data = OFData;
+    static constexpr int kArrays = 6, kKeep = kOfKeep;
+    static constexpr double kRefusedMu = INFINITY;
+    static __device__ __forceinline__ void load(Wave* Wv, const Base* __restrict__ base, int lane) {
+        of_load(Wv, base, lane);
     }
-    for (int i = lane + 64 * kOfKeep; i < n; i += 64) {
-        sp += of_phase(Wv, d.t[i], d.tau0[i], d.nu[i], d.nud[i]);
-        sy += d.y[i];
+    static __device__ __forceinline__ bool apply(Wave* Wv, const Base* __restrict__ base,
+                                                 const TFMap* __restrict__ map, double v, int lane) {
+        return of_apply(Wv, base, map, v, lane);
     }
-    sp = wave_sum(sp);
-    sy = wave_sum(sy);
-    const double mp = sp / (double)n, my = sy / (double)n;
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < kOfKeep; ++k) {
-        const int i = lane + 64 * k;
-        if (i < n) {
-            const double mu = keep[k] - mp;
-            const double s = d.e[i];
-            const double r = ((d.y[i] - my) - mu) / s;
-            acc += r * r + log((2.0 * 3.141592653589793) * (s * s));
-            if (mu_out) mu_out[i] = mu;
-        }
+    static __device__ __forceinline__ double phase(const Wave* Wv, const Data& d, int i) {
+        return of_phase(Wv, d.a[0][i], d.a[3][i], d.a[4][i], d.a[5][i]);
     }
-    for (int i = lane + 64 * kOfKeep; i < n; i += 64) {
-        const double mu = of_phase(Wv, d.t[i], d.tau0[i], d.nu[i], d.nud[i]) - mp;
-        const double s = d.e[i];
-        const double r = ((d.y[i] - my) - mu) / s;
-        acc += r * r + log((2.0 * 3.141592653589793) * (s * s));
-        if (mu_out) mu_out[i] = mu;
-    }
-    return 0.5 * wave_sum(acc);
-}
-
-// k_timing_nll's launch shape: block b = (problem, group of kTfNllWaves vectors)
-__global__ __launch_bounds__(kTfNllWaves * 64) void k_orbit_nll(
-    const double* __restrict__ t, const double* __restrict__ y, const double* __restrict__ e,
-    const double* __restrict__ consts, int64_t ntoa, const int64_t* __restrict__ off,
-    const OFModel* __restrict__ models, const TFMap* __restrict__ map, const double* __restrict__ pvec, int64_t P,
-    int64_t groups, double* __restrict__ nll, double* __restrict__ mu) {
-    __shared__ OFWave sm[kTfNllWaves];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t prob = blockIdx.x / groups;
-    const int64_t p = (blockIdx.x - prob * groups) * kTfNllWaves + wave;
-    if (p >= P) return;  // no block-wide barrier below: a wave works alone
-    const int nd = map->ndim;
-    const int64_t o = off[prob];
-    const int n = (int)(off[prob + 1] - o);
-    OFWave* Wv = &sm[wave];
-    of_load(Wv, models + prob, lane);
-    const double v = lane < nd ? pvec[(prob * P + p) * nd + lane] : 0.0;
-    const bool ok = of_apply(Wv, models + prob, map, v, lane);
-    double* mo = mu ? mu + P * o + p * (int64_t)n : nullptr;
-    double r = INFINITY;
-    if (ok) {
-        const OFData d = {t + o, y + o, e + o, consts + o, consts + ntoa + o, consts + 2 * ntoa + o};
-        r = of_nll(Wv, d, n, mo, lane);
-    } else if (mo) {
-        for (int i = lane; i < n; i += 64) mo[i] = INFINITY;
-    }
-    if (lane == 0) nll[prob * P + p] = r;
-}
-
-// k_timing_mcmc on of_nll: the same walkers, halves, move, counters and outputs. The staged arrays (stage != 0) are
-// the problem's ToAs and their constants, [6][n].
-__global__ __launch_bounds__(kTfMcWaves * 64) void k_orbit_mcmc(
-    const double* __restrict__ t, const double* __restrict__ y, const double* __restrict__ e,
-    const double* __restrict__ consts, int64_t ntoa, const int64_t* __restrict__ off,
-    const OFModel* __restrict__ models, const TFMap* __restrict__ map, const double* __restrict__ p0,
-    const double* __restrict__ lo, const double* __restrict__ hi, int W, int64_t steps, uint64_t seed,
-    int64_t first_problem, int stage, double* __restrict__ chain, double* __restrict__ logprob,
-    int64_t* __restrict__ accepted) {
-    extern __shared__ double of_sm[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t prob = blockIdx.x;
-    const int nd = map->ndim;
-    const int64_t o = off[prob];
-    const int n = (int)(off[prob + 1] - o);
-    double* pos = of_sm;                                             // [W][nd]
-    double* lp = pos + W * nd;                                       // [W]
-    long long* nacc = reinterpret_cast<long long*>(lp + W);          // [W]
-    OFWave* Wv = reinterpret_cast<OFWave*>(nacc + W) + wave;         // [kTfMcWaves]
-    double* st = reinterpret_cast<double*>(reinterpret_cast<OFWave*>(nacc + W) + kTfMcWaves);  // [6][n] if staged
-    OFData d = {t + o, y + o, e + o, consts + o, consts + ntoa + o, consts + 2 * ntoa + o};
-    if (stage) {
-        for (int i = threadIdx.x; i < n; i += blockDim.x) {
-            st[i] = d.t[i];
-            st[n + i] = d.y[i];
-            st[2 * n + i] = d.e[i];
-            st[3 * n + i] = d.tau0[i];
-            st[4 * n + i] = d.nu[i];
-            st[5 * n + i] = d.nud[i];
-        }
-        d = {st, st + n, st + 2 * n, st + 3 * n, st + 4 * n, st + 5 * n};
-    }
-    for (int i = threadIdx.x; i < W * nd; i += blockDim.x) pos[i] = p0[prob * W * nd + i];
-    for (int i = threadIdx.x; i < W; i += blockDim.x) nacc[i] = 0;
-    const OFModel* base = models + prob;
-    of_load(Wv, base, lane);
-    const double blo = lane < nd ? lo[prob * nd + lane] : 0.0, bhi = lane < nd ? hi[prob * nd + lane] : 0.0;
-    __syncthreads();
-    // log-probability of the starting positions (outside the box, an orbit outside the limits, a non-finite value: -inf)
-    for (int w = wave; w < W; w += kTfMcWaves) {
-        const double x = lane < nd ? pos[w * nd + lane] : 0.0;
-        const bool in = lane >= nd || (blo < x && x < bhi);
-        double l = -INFINITY;
-        if (__all(in) && of_apply(Wv, base, map, x, lane)) {
-            l = -of_nll(Wv, d, n, nullptr, lane);
-            if (!isfinite(l)) l = -INFINITY;
-        }
-        if (lane == 0) lp[w] = l;
-    }
-    __syncthreads();
-    const int half = W / 2;
-    const uint32_t gp = (uint32_t)(first_problem + prob);
-    for (int64_t s = 0; s < steps; ++s) {
-        for (int h = 0; h < 2; ++h) {
-            for (int k = wave; k < half; k += kTfMcWaves) {
-                const int w = 2 * k + h;
-                uint32_t r[4];
-                tf_philox(gp, (uint32_t)s, (uint32_t)w, 0u, seed, r);
-                const double u = tf_uniform(r[0], r[1]);
-                const int cw = 2 * (int)__umulhi(r[2], (uint32_t)half) + (1 - h);
-                const double zr = u + 1.0;  // (a - 1) u + 1, a = 2
-                const double z = zr * zr * 0.5;
-                const double x = lane < nd ? pos[w * nd + lane] : 0.0;
-                const double c = lane < nd ? pos[cw * nd + lane] : 0.0;
-                const double q = c - (c - x) * z;
-                const bool in = lane >= nd || (blo < q && q < bhi);
-                const double lold = lp[w];
-                double lnew = -INFINITY;
-                bool ok = __all(in);
-                if (ok) ok = of_apply(Wv, base, map, q, lane);  // an orbit outside the limits is not evaluated
-                if (ok) {
-                    lnew = -of_nll(Wv, d, n, nullptr, lane);
-                    ok = isfinite(lnew);
-                }
-                if (ok) {
-                    tf_philox(gp, (uint32_t)s, (uint32_t)w, 1u, seed, r);
-                    ok = log(tf_uniform(r[0], r[1])) < (double)(nd - 1) * log(z) + lnew - lold;
-                }
-                if (ok) {
-                    if (lane < nd) pos[w * nd + lane] = q;
-                    if (lane == 0) {
-                        lp[w] = lnew;
-                        nacc[w] += 1;
-                    }
-                }
-                const int64_t row = (prob * steps + s) * W + w;
-                if (lane < nd) chain[row * nd + lane] = ok ? q : x;
-                if (lane == 0) logprob[row] = ok ? lnew : lold;
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = threadIdx.x; i < W; i += blockDim.x) accepted[prob * W + i] = nacc[i];
-}
+};

@@ -1,7 +1,7 @@
 // photon_fit.h -- photon-domain timing fits: the unbinned template likelihood of every photon folded with a corrected
 // timing model, for P correction vectors at once, and the ensemble sampler of it. Not in the reference.
 // Included by crimp_hip.hip after cp_one, TplDev / tpl_coef / photon_sincos_tab / tpl_terms, wave_sum / wave_min and
-// tf_philox / tf_uniform; the host plan is photon_fit_plan.h, the C-ABI (crimp_photon_nll, crimp_photon_mcmc) is in
+// stretch_move.h; the host plan is photon_fit_plan.h, the C-ABI (crimp_photon_nll, crimp_photon_mcmc) is in
 // crimp_hip.hip's section 6.
 //
 //   delta_i(p) = cp_one(photon fit model of p, t_i)      (= Phi(t_i; par) - Phi(t_i; par - p), photon_fit_plan.h)
@@ -163,22 +163,18 @@ struct PFMc {
     int64_t* accepted;           // [W]
 };
 
-// the stretch proposals of half h at step s (k_timing_mcmc's move and random stream, problem index 0)
+// the stretch proposals of half h at step s (stretch_move.h's move and random stream, problem index 0)
 __device__ __forceinline__ void pf_propose(const PFMc& A, int64_t s, int h, int wave, int lane) {
     const int D = A.D, half = A.W / 2;
     const double blo = lane < D ? A.lo[lane] : 0.0, bhi = lane < D ? A.hi[lane] : 0.0;
     for (int k = wave; k < half; k += kPfStepWaves) {
         const int w = 2 * k + h;
-        uint32_t r[4];
-        tf_philox(0u, (uint32_t)s, (uint32_t)w, 0u, A.seed, r);
-        const double u = tf_uniform(r[0], r[1]);
-        const int cw = 2 * (int)__umulhi(r[2], (uint32_t)half) + (1 - h);
-        const double zr = u + 1.0;  // (a - 1) u + 1, a = 2
-        const double z = zr * zr * 0.5;
+        int cw;
+        const double z = sm_draw(A.seed, 0u, s, w, half, h, &cw);
         const double x = lane < D ? A.pos[w * D + lane] : 0.0;
         const double c = lane < D ? A.pos[cw * D + lane] : 0.0;
-        const double q = c - (c - x) * z;
-        const bool in = lane >= D || (blo < q && q < bhi);
+        bool in;
+        const double q = sm_propose(x, c, z, blo, bhi, lane >= D, &in);
         const bool ok = __all(in);
         if (lane < D) A.prop[k * D + lane] = q;
         if (lane == 0) {
@@ -235,11 +231,7 @@ __global__ __launch_bounds__(kPfStepWaves * 64) void k_photon_step(PFMc A, int m
             lnew = -pf_reduce(A.psum + k * A.tiles, A.pmin + k * A.tiles, A.tiles, A.n, A.norm, lane);
             ok = isfinite(lnew);
         }
-        if (ok) {
-            uint32_t r[4];
-            tf_philox(0u, (uint32_t)s, (uint32_t)w, 1u, A.seed, r);
-            ok = log(tf_uniform(r[0], r[1])) < (double)(D - 1) * log(z) + lnew - lold;
-        }
+        if (ok) ok = sm_accept(A.seed, 0u, s, w, D, z, lnew, lold);
         if (ok) {
             if (lane < D) A.pos[w * D + lane] = q;
             if (lane == 0) {

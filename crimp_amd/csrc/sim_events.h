@@ -1,8 +1,8 @@
 // sim_events.h -- event simulator: photon arrival times of an inhomogeneous Poisson process whose rate follows a
 // pulse profile under a timing model (replaces simulatemodulatedlc.py:19-96 of the reference, a binned sinusoid at
 // constant frequency drawn from NumPy's global RNG, and the host generators of crimp_amd/synth.py). Included by
-// crimp_hip.hip after cp_one, TplDev / tpl_coef / photon_sincos / tpl_terms and tf_philox / tf_uniform; the C-ABI
-// (crimp_sim_events) is in its section 6.
+// crimp_hip.hip after cp_one, TplDev / tpl_coef / photon_sincos / tpl_terms and stretch_move.h (tf_philox, tf_uniform);
+// the C-ABI (crimp_sim_events) is in its section 6.
 //
 // The process: on [mjd_start, mjd_start + span_s / 86400), inside the union of the half-open GTIs when given,
 //   lambda(t) = S(frac(phi(t))) + b   counts/s,

@@ -17,8 +17,7 @@ import pandas as pd
 
 from . import ops
 from .binarymodels import _tiny_units, binary_params, has_binary
-from .fit_toas import (DeviceSampler, _load_toas, _report_and_patch, build_parser, plot_residuals, prior_box,
-                       summarize_chain)
+from .fit_toas import _load_toas, _report_and_patch, build_parser, plot_residuals, sample_posterior
 from .logging_utils import get_logger
 from .readtimingmodel import BINARY_MODELS, ReadTimingModel, get_parameter_value, patch_par_values
 from .timfile import readtimfile
@@ -218,26 +217,11 @@ def run_mcmc(x, y, yerr, init_parfile: dict, keys: list[str], prior: Prior, step
     """``fit_toas.run_mcmc`` on ``crimp_orbit_mcmc``: walkers start uniform inside the prior box (a start outside the
     orbit's limits has log-probability -inf and is left by the first accepted move). Returns (sampler, flat post-burn
     samples, summaries)."""
-    ndim = len(keys)
-    rng = np.random.default_rng(seed)
-    p0 = np.empty((walkers, ndim), dtype=float)
-    for i, name in enumerate(keys):
-        lo, hi = prior.bounds[name]
-        p0[:, i] = rng.uniform(lo, hi, size=walkers)
-    kernel_seed = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
-    prob = OrbitFit(x, init_parfile, keys, y, yerr)
-    lo, hi = prior_box(prior, keys)
-    chain, logprob, accepted = ops.orbit_mcmc(prob.x, prob.y, prob.yerr, prob.par, prob.fit_base, prob.wave_base,
-                                              prob.map, p0[None], lo[None], hi[None], steps, kernel_seed)
-    sampler = DeviceSampler(chain[0], logprob[0], accepted[0])
-    if chain_npy:
-        np.save(chain_npy, sampler.get_chain())
-    discard = max(0, burn)
-    flat = sampler.get_chain(discard=discard, flat=True)
-    flat_logprob = sampler.get_log_prob(discard=discard, flat=True)
-    if flat_npy:
-        np.save(flat_npy, flat)
-    return sampler, flat, summarize_chain(flat, flat_logprob, keys)
+    def mcmc(*box_steps_seed):
+        prob = OrbitFit(x, init_parfile, keys, y, yerr)
+        return ops.orbit_mcmc(prob.x, prob.y, prob.yerr, prob.par, prob.fit_base, prob.wave_base, prob.map,
+                              *box_steps_seed)
+    return sample_posterior(mcmc, keys, prior, steps, burn, walkers, chain_npy, flat_npy, seed)
 
 
 def patch_orbit_par(in_path, out_path, full, uncertainties=None):

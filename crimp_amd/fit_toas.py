@@ -110,6 +110,31 @@ def summarize_chain(flat, flat_logprob, keys):
     return out
 
 
+def sample_posterior(mcmc, keys: list[str], prior: Prior, steps, burn, walkers, chain_npy, flat_npy, seed):
+    """What every ``run_mcmc`` does around its sampler: walkers start uniform inside the prior box, ``mcmc(p0, lo, hi,
+    steps, kernel_seed)`` runs one problem's chain on the device (``ops.timing_mcmc`` or ``ops.orbit_mcmc`` on the
+    caller's problem), the first ``burn`` steps are discarded and the chains saved where asked. ``seed`` None draws the
+    kernel's seed; else it is the kernel's seed too. Returns (sampler, flat post-burn samples, summaries)."""
+    ndim = len(keys)
+    rng = np.random.default_rng(seed)
+    p0 = np.empty((walkers, ndim), dtype=float)
+    for i, name in enumerate(keys):
+        lo, hi = prior.bounds[name]
+        p0[:, i] = rng.uniform(lo, hi, size=walkers)
+    kernel_seed = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
+    lo, hi = prior_box(prior, keys)
+    chain, logprob, accepted = mcmc(p0[None], lo[None], hi[None], steps, kernel_seed)
+    sampler = DeviceSampler(chain[0], logprob[0], accepted[0])
+    if chain_npy:
+        np.save(chain_npy, sampler.get_chain())
+    discard = max(0, burn)
+    flat = sampler.get_chain(discard=discard, flat=True)
+    flat_logprob = sampler.get_log_prob(discard=discard, flat=True)
+    if flat_npy:
+        np.save(flat_npy, flat)
+    return sampler, flat, summarize_chain(flat, flat_logprob, keys)
+
+
 def run_mcmc(x, y, yerr, init_parfile: dict, keys: list[str], prior: Prior, steps: int = 10000, burn: int = 500,
              walkers: int = 32, corner_pdf: str | None = None, chain_npy: str | None = None,
              flat_npy: str | None = None, progress: bool = True, *, seed=None):
@@ -121,25 +146,11 @@ def run_mcmc(x, y, yerr, init_parfile: dict, keys: list[str], prior: Prior, step
             import corner
         except ImportError as e:
             raise ImportError("corner_pdf needs the 'corner' package, which is not installed") from e
-    ndim = len(keys)
-    rng = np.random.default_rng(seed)
-    p0 = np.empty((walkers, ndim), dtype=float)
-    for i, name in enumerate(keys):
-        lo, hi = prior.bounds[name]
-        p0[:, i] = rng.uniform(lo, hi, size=walkers)
-    kernel_seed = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
-    prob = DeviceFit(x, init_parfile, keys, y, yerr)
-    lo, hi = prior_box(prior, keys)
-    chain, logprob, accepted = ops.timing_mcmc(prob.x, prob.y, prob.yerr, prob.fit_base, prob.wave_base, prob.map,
-                                               p0[None], lo[None], hi[None], steps, kernel_seed)
-    sampler = DeviceSampler(chain[0], logprob[0], accepted[0])
-    if chain_npy:
-        np.save(chain_npy, sampler.get_chain())
-    discard = max(0, burn)
-    flat = sampler.get_chain(discard=discard, flat=True)
-    flat_logprob = sampler.get_log_prob(discard=discard, flat=True)
-    if flat_npy:
-        np.save(flat_npy, flat)
+
+    def mcmc(*box_steps_seed):
+        prob = DeviceFit(x, init_parfile, keys, y, yerr)
+        return ops.timing_mcmc(prob.x, prob.y, prob.yerr, prob.fit_base, prob.wave_base, prob.map, *box_steps_seed)
+    sampler, flat, summaries = sample_posterior(mcmc, keys, prior, steps, burn, walkers, chain_npy, flat_npy, seed)
     if corner_pdf is not None:
         import matplotlib.pyplot as plt
         fig = corner.corner(flat, bins=32, smooth=1.5, plot_datapoints=False, fill_contours=True, plot_density=True,
@@ -149,7 +160,7 @@ def run_mcmc(x, y, yerr, init_parfile: dict, keys: list[str], prior: Prior, step
         fig.subplots_adjust(hspace=0.13)
         fig.savefig(corner_pdf + ".pdf", format="pdf", dpi=300)
         plt.close(fig)
-    return sampler, flat, summarize_chain(flat, flat_logprob, keys)
+    return sampler, flat, summaries
 
 
 def rms_residual(phaseresid, model_phaseresid):

@@ -454,14 +454,20 @@ def fit_map(keys):
     return m
 
 
-def _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases):
+def _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases, pars=None):
+    """The pointers, counts and model arrays of a ToA-fit call; ``pars`` None: a binary-free fit, which refuses a base
+    with an orbit."""
     if isinstance(fit_bases, N.TimingModel):
         fit_bases, wave_bases = [fit_bases], [wave_bases]
+        pars = None if pars is None else [pars]
     nprob = len(fit_bases)
-    if len(wave_bases) != nprob:
-        raise ValueError("one fit base and one wave base per problem")
-    if any(m.binary for m in fit_bases) or any(m.binary for m in wave_bases):
-        raise ValueError("binary models are not fitted yet")
+    if pars is None:
+        if len(wave_bases) != nprob:
+            raise ValueError("one fit base and one wave base per problem")
+        if any(m.binary for m in fit_bases) or any(m.binary for m in wave_bases):
+            raise ValueError("binary models are not fitted yet")
+    elif len(pars) != nprob or len(wave_bases) != nprob:
+        raise ValueError("one full model, one fit base and one wave base per problem")
     if offsets is None:
         n = int(t.numel() if N._is_torch(t) else np.size(t))
         offsets = np.array([0, n], dtype=np.int64)
@@ -470,20 +476,17 @@ def _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases):
             offsets = torch.as_tensor(offsets, device=t.device)
     if int((offsets.numel() if N._is_torch(offsets) else np.size(offsets)) - 1) != nprob:
         raise ValueError("offsets needs one entry more than there are problems")
-    ptrs = (b.arg(t, np.float64), b.arg(y, np.float64), b.arg(yerr, np.float64), b.arg(offsets, np.int64))
+    ptrs = (b.arg(t, np.float64), b.arg(y, np.float64), b.arg(yerr, np.float64), b.arg(offsets, np.int64), nprob)
     ntoa = int(t.numel() if N._is_torch(t) else np.size(t))
-    return ptrs, nprob, ntoa, (N.TimingModel * nprob)(*fit_bases), (N.TimingModel * nprob)(*wave_bases)
+    arr = N.TimingModel * nprob
+    models = (() if pars is None else (arr(*pars),)) + (arr(*fit_bases), arr(*wave_bases))
+    return ptrs, nprob, ntoa, models
 
 
-def timing_nll(t, y, yerr, fit_bases, wave_bases, fmap, pvec, offsets=None, want_mu=False, flags=0):
-    """Gaussian NLL of the phase residuals for nprob problems x P parameter vectors in one launch (crimp_timing_nll).
-    ``t, y, yerr``: the ToAs of all problems concatenated, problem i = [offsets[i], offsets[i+1]) (offsets None: one
-    problem); ``fit_bases`` / ``wave_bases``: one N.TimingModel each per problem (or a single one);
-    ``pvec`` [nprob, P, ndim]. Returns nll [nprob, P], or (nll, mu) with ``want_mu``: mu flat, problem i's
-    mean-subtracted model residuals at mu[P * offsets[i]:] as [P, n_i]."""
+def _fit_nll(t, y, yerr, pars, fit_bases, wave_bases, fmap, pvec, offsets, want_mu, flags):
     L = N.load()
     b = N.Buffers()
-    (tp, yp, ep, op), nprob, ntoa, fb, wb = _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases)
+    ptrs, nprob, ntoa, models = _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases, pars)
     nd = int(fmap.ndim)
     tot = int(pvec.numel() if N._is_torch(pvec) else np.size(pvec))
     if nd < 1 or tot == 0 or tot % (nprob * nd):
@@ -494,22 +497,26 @@ def timing_nll(t, y, yerr, fit_bases, wave_bases, fmap, pvec, offsets=None, want
     mu = _empty_like_input(t, P * ntoa, b) if want_mu else None
     nllp = b.arg(nll, np.float64, writable=True)
     mup = b.arg(mu, np.float64, writable=True) if want_mu else None
+    call = L.crimp_timing_nll if pars is None else L.crimp_orbit_nll
     with b.device_guard():
-        N.check(L.crimp_timing_nll(tp, yp, ep, op, nprob, fb, wb, ctypes.byref(fmap), pp, P, nllp, mup,
-                                   b.flags(flags), b.stream()))
+        N.check(call(*ptrs, *models, ctypes.byref(fmap), pp, P, nllp, mup, b.flags(flags), b.stream()))
     nll = nll.reshape(nprob, P)
     return (nll, mu) if want_mu else nll
 
 
-def timing_mcmc(t, y, yerr, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets=None, first_problem=0,
-                flags=0):
-    """The ensemble sampler of nprob problems in one launch (crimp_timing_mcmc): ``p0`` [nprob, W, ndim], ``lo`` /
-    ``hi`` [nprob, ndim] (+-inf: no bound). Returns (chain [nprob, steps, W, ndim], logprob [nprob, steps, W],
-    accepted [nprob, W]); placement follows ``t``. Problem i draws the random stream of global index
-    ``first_problem + i``."""
+def _chain_outputs(b, like, nprob, steps, W, D):
+    """(chain, logprob, accepted) of nprob chains, flat, placed as ``like``, and their writable pointers."""
+    rows = nprob * max(steps, 0) * W
+    out = (_empty_like_input(like, rows * D, b), _empty_like_input(like, rows, b),
+           _empty_like_input(like, nprob * W, b, dtype=np.int64))
+    return out, (b.arg(out[0], np.float64, writable=True), b.arg(out[1], np.float64, writable=True),
+                 b.arg(out[2], np.int64, writable=True))
+
+
+def _fit_mcmc(t, y, yerr, pars, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets, first_problem, flags):
     L = N.load()
     b = N.Buffers()
-    (tp, yp, ep, op), nprob, ntoa, fb, wb = _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases)
+    ptrs, nprob, ntoa, models = _fit_args(b, t, y, yerr, offsets, fit_bases, wave_bases, pars)
     nd = int(fmap.ndim)
     shape = tuple(p0.shape)
     if len(shape) != 3 or shape[0] != nprob or shape[2] != nd:
@@ -519,18 +526,31 @@ def timing_mcmc(t, y, yerr, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed
         if int(a.numel() if N._is_torch(a) else np.size(a)) != nprob * nd:
             raise ValueError("lo and hi must be [nprob, ndim]")
     pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
-    rows = nprob * max(steps, 0) * W
-    chain = _empty_like_input(t, rows * nd, b)
-    logprob = _empty_like_input(t, rows, b)
-    accepted = _empty_like_input(t, nprob * W, b, dtype=np.int64)
-    cp = b.arg(chain, np.float64, writable=True)
-    lpp = b.arg(logprob, np.float64, writable=True)
-    ap = b.arg(accepted, np.int64, writable=True)
+    (chain, logprob, accepted), outp = _chain_outputs(b, t, nprob, steps, W, nd)
+    call = L.crimp_timing_mcmc if pars is None else L.crimp_orbit_mcmc
     with b.device_guard():
-        N.check(L.crimp_timing_mcmc(tp, yp, ep, op, nprob, fb, wb, ctypes.byref(fmap), pp, lop, hip_, W, steps,
-                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_problem), cp, lpp, ap, b.flags(flags),
-                                    b.stream()))
+        N.check(call(*ptrs, *models, ctypes.byref(fmap), pp, lop, hip_, W, steps, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                     int(first_problem), *outp, b.flags(flags), b.stream()))
     return chain.reshape(nprob, steps, W, nd), logprob.reshape(nprob, steps, W), accepted.reshape(nprob, W)
+
+
+def timing_nll(t, y, yerr, fit_bases, wave_bases, fmap, pvec, offsets=None, want_mu=False, flags=0):
+    """Gaussian NLL of the phase residuals for nprob problems x P parameter vectors in one launch (crimp_timing_nll).
+    ``t, y, yerr``: the ToAs of all problems concatenated, problem i = [offsets[i], offsets[i+1]) (offsets None: one
+    problem); ``fit_bases`` / ``wave_bases``: one N.TimingModel each per problem (or a single one);
+    ``pvec`` [nprob, P, ndim]. Returns nll [nprob, P], or (nll, mu) with ``want_mu``: mu flat, problem i's
+    mean-subtracted model residuals at mu[P * offsets[i]:] as [P, n_i]."""
+    return _fit_nll(t, y, yerr, None, fit_bases, wave_bases, fmap, pvec, offsets, want_mu, flags)
+
+
+def timing_mcmc(t, y, yerr, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets=None, first_problem=0,
+                flags=0):
+    """The ensemble sampler of nprob problems in one launch (crimp_timing_mcmc): ``p0`` [nprob, W, ndim], ``lo`` /
+    ``hi`` [nprob, ndim] (+-inf: no bound). Returns (chain [nprob, steps, W, ndim], logprob [nprob, steps, W],
+    accepted [nprob, W]); placement follows ``t``. Problem i draws the random stream of global index
+    ``first_problem + i``."""
+    return _fit_mcmc(t, y, yerr, None, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets, first_problem,
+                     flags)
 
 
 # names a .par gives the orbit fields under: XDOT is A1DOT, E is ECC, TASC takes T0's slot under ELL1
@@ -563,77 +583,18 @@ def orbit_fit_map(keys):
     return m
 
 
-def _orbit_args(b, t, y, yerr, offsets, pars, fit_bases, wave_bases):
-    if isinstance(pars, N.TimingModel):
-        pars, fit_bases, wave_bases = [pars], [fit_bases], [wave_bases]
-    nprob = len(pars)
-    if len(fit_bases) != nprob or len(wave_bases) != nprob:
-        raise ValueError("one full model, one fit base and one wave base per problem")
-    if offsets is None:
-        n = int(t.numel() if N._is_torch(t) else np.size(t))
-        offsets = np.array([0, n], dtype=np.int64)
-        if N._is_torch(t) and t.is_cuda:
-            import torch
-            offsets = torch.as_tensor(offsets, device=t.device)
-    if int((offsets.numel() if N._is_torch(offsets) else np.size(offsets)) - 1) != nprob:
-        raise ValueError("offsets needs one entry more than there are problems")
-    ptrs = (b.arg(t, np.float64), b.arg(y, np.float64), b.arg(yerr, np.float64), b.arg(offsets, np.int64))
-    ntoa = int(t.numel() if N._is_torch(t) else np.size(t))
-    arr = N.TimingModel * nprob
-    return ptrs, nprob, ntoa, arr(*pars), arr(*fit_bases), arr(*wave_bases)
-
-
 def orbit_nll(t, y, yerr, pars, fit_bases, wave_bases, fmap, pvec, offsets=None, want_mu=False, flags=0):
     """``timing_nll`` for models with an orbit (crimp_orbit_nll): ``pars`` is the full model of every problem, with its
     binary block; ``fmap`` an ``orbit_fit_map``. A vector whose corrected orbit is outside the limits gives +inf."""
-    L = N.load()
-    b = N.Buffers()
-    (tp, yp, ep, op), nprob, ntoa, pm, fb, wb = _orbit_args(b, t, y, yerr, offsets, pars, fit_bases, wave_bases)
-    nd = int(fmap.ndim)
-    tot = int(pvec.numel() if N._is_torch(pvec) else np.size(pvec))
-    if nd < 1 or tot == 0 or tot % (nprob * nd):
-        raise ValueError("pvec must be [nprob, P, ndim]")
-    P = tot // (nprob * nd)
-    pp = b.arg(pvec, np.float64)
-    nll = _empty_like_input(t, nprob * P, b)
-    mu = _empty_like_input(t, P * ntoa, b) if want_mu else None
-    nllp = b.arg(nll, np.float64, writable=True)
-    mup = b.arg(mu, np.float64, writable=True) if want_mu else None
-    with b.device_guard():
-        N.check(L.crimp_orbit_nll(tp, yp, ep, op, nprob, pm, fb, wb, ctypes.byref(fmap), pp, P, nllp, mup,
-                                  b.flags(flags), b.stream()))
-    nll = nll.reshape(nprob, P)
-    return (nll, mu) if want_mu else nll
+    return _fit_nll(t, y, yerr, pars, fit_bases, wave_bases, fmap, pvec, offsets, want_mu, flags)
 
 
 def orbit_mcmc(t, y, yerr, pars, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets=None, first_problem=0,
                flags=0):
     """``timing_mcmc`` for models with an orbit (crimp_orbit_mcmc); the arguments of ``orbit_nll`` and ``timing_mcmc``,
     the same outputs."""
-    L = N.load()
-    b = N.Buffers()
-    (tp, yp, ep, op), nprob, ntoa, pm, fb, wb = _orbit_args(b, t, y, yerr, offsets, pars, fit_bases, wave_bases)
-    nd = int(fmap.ndim)
-    shape = tuple(p0.shape)
-    if len(shape) != 3 or shape[0] != nprob or shape[2] != nd:
-        raise ValueError("p0 must be [nprob, W, ndim]")
-    W, steps = int(shape[1]), int(steps)
-    for a in (lo, hi):
-        if int(a.numel() if N._is_torch(a) else np.size(a)) != nprob * nd:
-            raise ValueError("lo and hi must be [nprob, ndim]")
-    pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
-    rows = nprob * max(steps, 0) * W
-    chain = _empty_like_input(t, rows * nd, b)
-    logprob = _empty_like_input(t, rows, b)
-    accepted = _empty_like_input(t, nprob * W, b, dtype=np.int64)
-    cp = b.arg(chain, np.float64, writable=True)
-    lpp = b.arg(logprob, np.float64, writable=True)
-    ap = b.arg(accepted, np.int64, writable=True)
-    with b.device_guard():
-        N.check(L.crimp_orbit_mcmc(tp, yp, ep, op, nprob, pm, fb, wb, ctypes.byref(fmap), pp, lop, hip_, W, steps,
-                                   int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_problem), cp, lpp, ap, b.flags(flags),
-                                   b.stream()))
-    return chain.reshape(nprob, steps, W, nd), logprob.reshape(nprob, steps, W), accepted.reshape(nprob, W)
+    return _fit_mcmc(t, y, yerr, pars, fit_bases, wave_bases, fmap, p0, lo, hi, steps, seed, offsets, first_problem,
+                     flags)
 
 
 def _photon_args(b, t, x, par, phoff):
@@ -685,17 +646,11 @@ def photon_mcmc(t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff=False
         if int(a.numel() if N._is_torch(a) else np.size(a)) != D:
             raise ValueError("lo and hi must be [%d]" % D)
     pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
-    rows = max(steps, 0) * W
-    chain = _empty_like_input(t, rows * D, b)
-    logprob = _empty_like_input(t, rows, b)
-    accepted = _empty_like_input(t, W, b, dtype=np.int64)
-    cp = b.arg(chain, np.float64, writable=True)
-    lpp = b.arg(logprob, np.float64, writable=True)
-    ap = b.arg(accepted, np.int64, writable=True)
+    (chain, logprob, accepted), outp = _chain_outputs(b, t, 1, steps, W, D)
     with b.device_guard():
         N.check(L.crimp_photon_mcmc(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph,
-                                    pp, lop, hip_, W, steps, int(seed) & 0xFFFFFFFFFFFFFFFF, cp, lpp, ap,
-                                    b.flags(flags), b.stream()))
+                                    pp, lop, hip_, W, steps, int(seed) & 0xFFFFFFFFFFFFFFFF, *outp, b.flags(flags),
+                                    b.stream()))
     return chain.reshape(steps, W, D), logprob.reshape(steps, W), accepted
 
 

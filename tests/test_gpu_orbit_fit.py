@@ -249,6 +249,30 @@ def test_mcmc_logprob_and_accepted(gpu, fixture, name, n):
     assert np.all((ch > lo) & (ch < hi))
 
 
+@pytest.mark.gpu
+def test_chain_is_the_same_bits_staged_in_lds_or_read_from_global_memory(gpu, fixture):
+    """Staging is decided by the call's largest problem: 3000 ToAs (6 doubles each) exceed the 128 KiB of LDS, so in
+    the pair [small, large] both problems read their ToAs and constants from global memory; alone, the small one is
+    staged. W = 2 ndim + 2 = 16: the case has seven free keys, and a call with fewer than 2 ndim walkers is refused."""
+    from crimp_amd.fit_orbit import OrbitFit
+    c = fixture[("ell1_amxp", 65)]
+    small = problem(c)
+    rng = np.random.default_rng(3000)
+    n = 3000
+    assert 6 * 8 * n > 128 * 1024
+    large = OrbitFit(np.sort(rng.uniform(c.t.min(), c.t.max(), n)), flagged(c.tm, c.keys), c.keys,
+                     rng.normal(0, 0.01, n), np.full(n, 0.01))
+    W, steps = 2 * len(c.keys) + 2, 10
+    starts = [walkers(c, W, 21), walkers(c, W, 22)]
+    alone = sample(small, *starts[0], steps, 31)
+    pair = many([small, large], mcmc=([s[0] for s in starts], [s[1] for s in starts], [s[2] for s in starts], steps,
+                                      31, 0))
+    for a, b in zip(alone, pair):
+        np.testing.assert_array_equal(a, b[0])
+    nll, _ = evaluate(large, pair[0][1].reshape(-1, len(c.keys)))
+    np.testing.assert_array_equal(pair[1][1].reshape(-1), -nll)
+
+
 # ------------------------------------------------------------------ 6. injection and recovery
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(O.INJECTION))

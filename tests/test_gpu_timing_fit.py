@@ -247,6 +247,36 @@ def test_sampler_determinism_and_sharding(gpu, side, case_a):
         np.testing.assert_array_equal(full[2:], t)
 
 
+@pytest.mark.gpu
+def test_chain_is_the_same_bits_staged_in_lds_or_read_from_global_memory(gpu, side, case_a):
+    """Staging is decided by the call's largest problem: 6000 ToAs (3 doubles each) exceed the 128 KiB of LDS, so in
+    the pair [small, large] both problems read their ToAs from global memory; alone, the small one is staged."""
+    from crimp_amd import ops
+    from crimp_amd.utilities_fittoas import DeviceFit
+    g, sol, sig = case_a
+    c = side["cases"]["a"]
+    small = device_fit(side, g, "a", 65)
+    rng = np.random.default_rng(6000)
+    n = 6000
+    assert 3 * 8 * n > 128 * 1024
+    large = DeviceFit(np.sort(rng.uniform(small.x.min(), small.x.max(), n)), copy.deepcopy(c["model"]), c["keys"],
+                      rng.normal(0, 0.01, n), np.full(n, 0.01))
+    W, steps = 8, 10
+    p0 = sol + rng.uniform(-3, 3, (2, W, 2)) * sig
+    lo, hi = sol - 50 * sig, sol + 50 * sig
+    alone = run_chain(small, p0[0], lo, hi, steps, 7)
+    fits = [small, large]
+    off = np.array([0, 65, 65 + n], dtype=np.int64)
+    pair = ops.timing_mcmc(np.concatenate([f.x for f in fits]), np.concatenate([f.y for f in fits]),
+                           np.concatenate([f.yerr for f in fits]), [f.fit_base for f in fits],
+                           [f.wave_base for f in fits], small.map, p0, np.tile(lo, (2, 1)), np.tile(hi, (2, 1)), steps,
+                           7, offsets=off, first_problem=0)
+    for a, b in zip(alone, pair):
+        np.testing.assert_array_equal(a[0], b[0])
+    nll, _ = evaluate(large, pair[0][1].reshape(-1, 2))
+    np.testing.assert_array_equal(pair[1][1].reshape(-1), -nll)
+
+
 # ------------------------------------------------------------------ 5. posterior
 MEDIAN_TOL, WIDTH_TOL, ACCEPT_RANGE = 0.15, 0.08, (0.55, 0.85)
 

@@ -5,11 +5,15 @@
   chains       32 walkers x 10000 steps: crimp_timing_mcmc, and crimp_orbit_mcmc for both orbits with every key free
 REPS timed repeats (default 5) after one warm-up, the binary-free and the orbit calls alternating.
 
---parent-lib PATH: another build of the library (the parent commit's). crimp_timing_nll then runs in fresh child
-processes, the two builds alternating (ROUNDS rounds, default 3); the report holds each build's times, their spread, and
-whether nll and mu are the same bits.
+--parent-lib PATH: another build of the library (the parent commit's). Both builds then run in fresh child processes,
+one library per process (CRIMP_LIB), alternating for ROUNDS rounds (default 3; the first build of a round alternates
+too). A child prints SHA-256 digests of what all six fit entry points and crimp_sim_events write at the shapes of the
+tests, and REPS kernel times of the NLL at P = 4096 x 84 ToAs (binary-free, BT e = 0.7, ELL1), of the 32 x 10000
+chains of the three and of the photon chain of tools/run_photon_fit.py (N = 1e5). The report holds every digest of
+both builds and whether they are equal, and per shape each build's median with the spread of its round medians.
 One JSON line, also written to profiles/orbit_fit.json."""
 import argparse
+import copy
 import hashlib
 import json
 import os
@@ -21,6 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from crimp_amd import _native as N, ops  # noqa: E402
 from crimp_amd.fit_orbit import OrbitFit  # noqa: E402
 from crimp_amd.fit_toas import load_toas_for_fit  # noqa: E402
@@ -30,6 +35,7 @@ from crimp_amd.utilities_fittoas import DeviceFit, list_fit_keys  # noqa: E402
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 P = 4096
+W, STEPS = 32, 10000
 reps = int(os.environ.get("REPS", 5))
 ORBITS = {
     "bt_e07": ({"BINARY": "BT", "PB": 8.3, "A1": 20.0, "ECC": 0.7, "OM": 200.0, "T0": 0.3},
@@ -51,83 +57,20 @@ def bundled():
     return model, toas
 
 
-def timing_only(lib_path, data_path):
-    """crimp_timing_nll of the build at ``lib_path`` on the ToAs saved at ``data_path``: kernel times and a digest of
-    its outputs. The library is bound here, entry point by entry point: the parent's build has no orbit symbols for
-    crimp_amd._native to bind."""
-    import ctypes
-    d = np.load(data_path)
-    model = ReadTimingModel(os.path.join(GOLD, "1e2259.par")).readfulltimingmodel()[2]
-    model["F0"]["flag"] = model["F1"]["flag"] = 1
-    fit = DeviceFit(d["x"], model, list_fit_keys(model), d["y"], d["e"])
-    pv = np.random.default_rng(0).normal(0, 1, (1, P, 2)) * np.array(SPIN_SCALE)
-    L = ctypes.CDLL(lib_path)
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    MP, FP = ctypes.POINTER(N.TimingModel), ctypes.POINTER(N.FitMap)
-    L.crimp_timing_nll.argtypes = [vp, vp, vp, vp, i64, MP, MP, FP, vp, i64, vp, vp, ctypes.c_uint32, vp]
-    L.crimp_last_kernel_times.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
-    L.crimp_last_error.restype = ctypes.c_char_p
-    n = fit.x.size
-    off = np.array([0, n], dtype=np.int64)
-    nll, mu = np.empty(P), np.empty(P * n)
-    ms = (ctypes.c_double * 4)()
-    kern = []
-    for r in range(reps + 1):
-        rc = L.crimp_timing_nll(fit.x.ctypes.data, fit.y.ctypes.data, fit.yerr.ctypes.data, off.ctypes.data, 1,
-                                ctypes.byref(fit.fit_base), ctypes.byref(fit.wave_base), ctypes.byref(fit.map),
-                                pv.ctypes.data, P, nll.ctypes.data, mu.ctypes.data, N.FLAG_TIME_KERNELS, None)
-        if rc:
-            raise RuntimeError(L.crimp_last_error().decode())
-        L.crimp_last_kernel_times(ms, 4)
-        if r:
-            kern.append(ms[0])
-    digest = hashlib.sha256(nll.tobytes() + mu.tobytes()).hexdigest()
-    print(json.dumps({"kernel_ms": kern, "digest": digest}), flush=True)
-
-
-def compare_with(parent_lib, x, y, e):
-    import tempfile
-    rounds = int(os.environ.get("ROUNDS", 3))
-    runs = {"parent": [], "this": []}
-    digests = {"parent": set(), "this": set()}
-    libs = {"parent": os.path.abspath(parent_lib), "this": N.LIB_PATH}
-    with tempfile.TemporaryDirectory() as tmp:
-        data = os.path.join(tmp, "toas.npz")
-        np.savez(data, x=x, y=y, e=e)
-        for _ in range(rounds):
-            for which in ("parent", "this"):
-                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--timing-only", libs[which], data],
-                                     capture_output=True, text=True, timeout=300)
-                if res.returncode:
-                    raise RuntimeError("the %s build's run failed:\n%s" % (which, res.stderr[-2000:]))
-                got = json.loads(res.stdout.strip().splitlines()[-1])
-                runs[which] += got["kernel_ms"]
-                digests[which].add(got["digest"])
-    return {"rounds": rounds, "parent_kernel_ms": stat(runs["parent"]), "this_kernel_ms": stat(runs["this"]),
-            "bit_identical": digests["parent"] == digests["this"] and len(digests["this"]) == 1}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--timing-only", nargs=2, metavar=("LIB", "TOAS_NPZ"), default=None)
-    args = ap.parse_args()
-    if args.timing_only:
-        return timing_only(*args.timing_only)
+def workloads(rng):
+    """({name: (evaluations, call)}, {name: call}): the likelihood calls at P vectors and the 32 x 10000 chains."""
     model, toas = bundled()
     spin_keys = list_fit_keys(model)
     x, y, e = toas["ToA"].to_numpy(), toas["phase"].to_numpy(), toas["phase_err_cycle"].to_numpy()
-    rng = np.random.default_rng(0)
     free = DeviceFit(x, model, spin_keys, y, e)
     calls = {}
     pv = rng.normal(0, 1, (1, P, 2)) * np.array(SPIN_SCALE)
     calls["timing_nll"] = (P, lambda: ops.timing_nll(free.x, free.y, free.yerr, free.fit_base, free.wave_base, free.map,
                                                      pv, flags=N.FLAG_TIME_KERNELS))
-    W, steps = 32, 10000
     p0 = rng.normal(0, 1, (1, W, 2)) * np.array(SPIN_SCALE)
     inf = np.full((1, 2), np.inf)
     chains = {"timing_mcmc": lambda: ops.timing_mcmc(free.x, free.y, free.yerr, free.fit_base, free.wave_base, free.map,
-                                                     p0, -inf, inf, steps, 1, flags=N.FLAG_TIME_KERNELS)}
+                                                     p0, -inf, inf, STEPS, 1, flags=N.FLAG_TIME_KERNELS)}
     for name, (orbit, okeys, oscale) in ORBITS.items():
         tm = dict(model)
         for k, v in orbit.items():
@@ -143,10 +86,153 @@ def main():
         q0 = rng.normal(0, 1, (1, W, nd)) * np.array(scale)
         box = np.full((1, nd), np.inf)
         chains["orbit_mcmc_%s_all" % name] = lambda fit=fit, q0=q0, box=box: ops.orbit_mcmc(
-            fit.x, fit.y, fit.yerr, fit.par, fit.fit_base, fit.wave_base, fit.map, q0, -box, box, steps, 1,
+            fit.x, fit.y, fit.yerr, fit.par, fit.fit_base, fit.wave_base, fit.map, q0, -box, box, STEPS, 1,
             flags=N.FLAG_TIME_KERNELS)
-    out = {"reps": reps, "ntoa": int(x.size), "P": P}
-    for group, each in ((calls, None), (chains, W * steps)):
+    return x.size, calls, chains
+
+
+def sha(*arrays):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)).hexdigest()[:16]
+
+
+def photon_problem(n):
+    """tools/run_photon_fit.py's (F0, F1) problem on n photons."""
+    from crimp_amd.fit_photons import PhotonFit
+    from crimp_amd.readPPtemplate import readPPtemplate
+    par = ReadTimingModel(os.path.join(GOLD, "1e2259.par")).readfulltimingmodel()[2]
+    par["F0"]["flag"] = par["F1"]["flag"] = 1
+    t = np.sort(par["PEPOCH"]["value"] + np.random.default_rng(n).uniform(-1.0, 8.0, n))
+    return PhotonFit(t, par, readPPtemplate(os.path.join(GOLD, "1e2259_template.txt")), keys=["F0", "F1"])
+
+
+def digests():
+    """What the fit entry points and the simulator write at the shapes of the tests, as digests."""
+    import orbit_fit_reference as O
+    from crimp_amd.simulatemodulatedlc import simulatemodulatedlc
+    out = {}
+    with open(os.path.join(GOLD, "fittoas.json")) as fh:
+        case = json.load(fh)["cases"]["a"]
+    g = np.load(os.path.join(GOLD, "fittoas_nll_a.npz"))
+    for n in (63, 64, 65, 84, 257):
+        fit = DeviceFit(g["x_%d" % n], copy.deepcopy(case["model"]), case["keys"], g["y_%d" % n], g["e_%d" % n])
+        out["timing_nll_%d" % n] = sha(*ops.timing_nll(fit.x, fit.y, fit.yerr, fit.fit_base, fit.wave_base, fit.map,
+                                                       g["pvec"][None, :33], want_mu=True))
+    # the tight box of test_sampler_bookkeeping: proposals leave it
+    dt = (fit.x - case["model"]["PEPOCH"]["value"]) * 86400.0
+    A = np.stack([dt, 0.5 * dt * dt], axis=1)
+    A = A - A.mean(axis=0)
+    cov = np.linalg.inv(A.T @ (A / fit.yerr[:, None] ** 2))
+    sol, sig = cov @ (A.T @ ((fit.y - fit.y.mean()) / fit.yerr ** 2)), np.sqrt(np.diag(cov))
+    for Wn, steps in ((4, 50), (32, 200)):
+        p0 = sol + np.random.default_rng(Wn).uniform(-3, 3, (1, Wn, 2)) * sig
+        out["timing_mcmc_%d_%d" % (Wn, steps)] = sha(*ops.timing_mcmc(
+            fit.x, fit.y, fit.yerr, fit.fit_base, fit.wave_base, fit.map, p0, (sol - 4 * sig)[None],
+            (sol + 4 * sig)[None], steps, 11))
+    fixture = O.load_fixture()
+
+    def flagged(tm, keys):
+        return {k: {"value": v, "flag": None if k == "BINARY" else int(k in keys)} for k, v in tm.items()}
+    for name in ("bt_e07", "ell1_amxp"):
+        for n in (63, 64, 65, 257):
+            c = fixture[(name, n)]
+            rng = np.random.default_rng(n)
+            e = 1e-3 * rng.uniform(0.5, 1.5, c.n)
+            fit = OrbitFit(c.t, flagged(c.tm, c.keys), c.keys, c.mu_ref()[3] + e * rng.standard_normal(c.n), e)
+            args = (fit.x, fit.y, fit.yerr, fit.par, fit.fit_base, fit.wave_base, fit.map)
+            nd, w = len(c.keys), np.abs(c.pvec[3])
+            pv = rng.uniform(-3, 3, (33, nd)) * w
+            pv[5, c.keys.index("PB")] = 2 * float(c.tm["PB"])      # an orbit outside the limits: +inf rows
+            out["orbit_nll_%s_%d" % (name, n)] = sha(*ops.orbit_nll(*args, pv[None], want_mu=True))
+        for Wn, steps in ((2 * nd + 2, 50), (32, 200)):     # n = 257; the box is tight: proposals leave it
+            p0 = rng.uniform(-3, 3, (1, Wn, nd)) * w
+            out["orbit_mcmc_%s_%d_%d" % (name, Wn, steps)] = sha(*ops.orbit_mcmc(*args, p0, -4 * w[None], 4 * w[None],
+                                                                                 steps, 123))
+    # a flat likelihood in a box that reaches past ECC = 1 and A1 = 0 (test_inadmissible_orbits_never_enter_a_chain)
+    c = fixture[("bt_e07", 64)]
+    ecc, a1 = float(c.tm["ECC"]), float(c.tm["A1"])
+    fit = OrbitFit(c.t, flagged(c.tm, ["ECC", "A1"]), ["ECC", "A1"], np.zeros(c.n), np.full(c.n, 1e6))
+    rng = np.random.default_rng(3)
+    p0 = np.column_stack([rng.uniform(-0.2, 0.2, 32), rng.uniform(-5, 5, 32)])
+    out["orbit_mcmc_inadmissible"] = sha(*ops.orbit_mcmc(
+        fit.x, fit.y, fit.yerr, fit.par, fit.fit_base, fit.wave_base, fit.map, p0[None],
+        np.array([[ecc - 1.5, a1 - 60.0]]), np.array([[ecc + 0.5, a1 + 20.0]]), 600, 11))
+    pf = photon_problem(3 * N.photon_tile() + 17)       # the size of the photon tests' sampler fixture
+    scale = np.array([1e-9, 1e-16])
+    out["photon_nll"] = sha(ops.photon_nll(pf.t, pf.x, pf.par, pf.map, pf.tpl, pf.norm,
+                                           np.random.default_rng(33).uniform(-1, 1, (33, 2)) * scale))
+    for Wn, steps in ((4, 50), (32, 200)):
+        p0 = np.random.default_rng(Wn).uniform(-3, 3, (Wn, 2)) * scale
+        out["photon_mcmc_%d_%d" % (Wn, steps)] = sha(*ops.photon_mcmc(pf.t, pf.x, pf.par, pf.map, pf.tpl, pf.norm, p0,
+                                                                      -4 * scale, 4 * scale, steps, 11))
+    lc = simulatemodulatedlc(0.5, srcrate=2.0, exposure=2000.0, seed=3)
+    out["sim_events"] = sha(lc["assigned_t_wBgr"], lc["assigned_t_nobgr"])
+    return out
+
+
+def child():
+    """The digests and the kernel times of the build CRIMP_LIB names (this process loads no other)."""
+    import torch
+    out = {"lib": N.LIB_PATH, "digest": digests(), "kernel_ms": {}}
+    _, calls, chains = workloads(np.random.default_rng(0))
+    timed = {k: v[1] for k, v in calls.items() if not k.endswith("_spin")}
+    timed.update(chains)
+    pf = photon_problem(100000)
+    dev = torch.device("cuda:0")
+    scale = np.array([1e-9, 1e-16])
+    t, x = torch.as_tensor(pf.t, device=dev), torch.as_tensor(pf.x, device=dev)
+    p0 = torch.as_tensor(np.random.default_rng(1).uniform(-3, 3, (W, 2)) * scale, device=dev)
+    lo, hi = (torch.as_tensor(s * 1e3 * scale, device=dev) for s in (-1.0, 1.0))
+    timed["photon_mcmc_n100000"] = lambda: ops.photon_mcmc(t, x, pf.par, pf.map, pf.tpl, pf.norm, p0, lo, hi, STEPS, 5,
+                                                           flags=N.FLAG_TIME_KERNELS)
+    for k, fn in timed.items():
+        ms = []
+        for r in range(reps + 1):
+            fn()
+            if r:
+                ms.append(N.last_kernel_times()[0])
+        out["kernel_ms"][k] = ms
+    print(json.dumps(out), flush=True)
+
+
+def compare_with(parent_lib):
+    rounds = int(os.environ.get("ROUNDS", 3))
+    libs = {"parent": os.path.abspath(parent_lib), "this": N.LIB_PATH}
+    got = {"parent": [], "this": []}
+    for r in range(rounds):
+        for which in (("parent", "this"), ("this", "parent"))[r % 2]:     # neither build is always the first of a round
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True,
+                                 timeout=600, env=dict(os.environ, CRIMP_LIB=libs[which]))
+            if res.returncode:
+                raise RuntimeError("the %s build's run failed:\n%s" % (which, res.stderr[-2000:]))
+            got[which].append(json.loads(res.stdout.strip().splitlines()[-1]))
+            assert got[which][-1]["lib"] == libs[which]
+    names = list(got["this"][0]["digest"])
+    digest = {k: {w: sorted({r["digest"][k] for r in got[w]}) for w in got} for k in names}
+    times = {}
+    for k in got["this"][0]["kernel_ms"]:
+        times[k] = {}
+        for w in got:
+            med = [float(np.median(r["kernel_ms"][k])) for r in got[w]]
+            times[k][w] = {"median_ms": float(np.median([v for r in got[w] for v in r["kernel_ms"][k]])),
+                           "round_medians_ms": med, "spread_ms": max(med) - min(med)}
+        delta = times[k]["this"]["median_ms"] - times[k]["parent"]["median_ms"]
+        times[k]["within_parent_spread"] = bool(abs(delta) <= times[k]["parent"]["spread_ms"])
+        times[k]["not_slower"] = bool(delta <= times[k]["parent"]["spread_ms"])
+    return {"rounds": rounds, "reps": reps, "digest": digest,
+            "bit_identical": all(len(d["this"]) == 1 and d["this"] == d["parent"] for d in digest.values()),
+            "kernel_ms": times}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--child", action="store_true")
+    args = ap.parse_args()
+    if args.child:
+        return child()
+    ntoa, calls, chains = workloads(np.random.default_rng(0))
+    out = {"reps": reps, "ntoa": int(ntoa), "P": P}
+    for group, each in ((calls, None), (chains, W * STEPS)):
         wall = {k: [] for k in group}
         kern = {k: [] for k in group}
         for r in range(reps + 1):            # the calls alternate within every repeat
@@ -164,7 +250,7 @@ def main():
                       "evals_per_s_kernel": n / (float(np.median(kern[k])) * 1e-3)}
     print(json.dumps(out), flush=True)
     if args.parent_lib:
-        out["timing_nll_vs_parent"] = compare_with(args.parent_lib, x, y, e)
+        out["vs_parent"] = compare_with(args.parent_lib)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     with open(os.path.join(ROOT, "profiles", "orbit_fit.json"), "w") as fh:
         json.dump(out, fh, indent=1)
