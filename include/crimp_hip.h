@@ -366,6 +366,11 @@ int crimp_timing_nll(const double* t_mjd, const double* y, const double* yerr, c
  * outside the box is rejected without evaluating it, and so is one whose log-probability is not finite (the reference
  * lets emcee raise on NaN). Random numbers: Philox4x32-10, key = seed, counter = (first_problem + i, step, walker,
  * draw): a chain depends on the seed, the problem's global index and its own data, not on the rest of the launch.
+ * Key = (seed's low 32 bits, its high 32 bits); the index and the step enter by their low 32 bits. A 53-bit uniform of
+ * two output words is U(a, b) = (((a >> 5) << 26 | (b >> 6)) + 0.5) 2^-53 in fp64, in (0, 1]. Walker w = 2 k + h of
+ * half h reads draw 0 for u = U(word 0, word 1) and its partner, walker 2 floor(word 2 * (W / 2) / 2^32) + (1 - h) of
+ * the other half, and draw 1 for u' = U(word 0, word 1). tests/stream_reference.py restates this on the host and
+ * tests/test_gpu_sampler_replay.py holds every decision of the three samplers to it.
  * p0[nprob][W][ndim]; lo, hi [nprob][ndim]; W even, 2 ndim <= W <= 256; steps >= 1.
  * chain[nprob][steps][W][ndim], logprob[nprob][steps][W], accepted[nprob][W] (accepted moves per walker). */
 int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, const int64_t* offsets,
@@ -493,6 +498,13 @@ int crimp_gather_ranges(const double* t, int64_t n, const int64_t* lo, const int
  * trusts it). Time is cut into cells of cell_s seconds anchored at mjd_start; the events of a cell depend on (seed,
  * model, shape, mjd_start, span_s, cell_s, GTIs, the cell's index) alone, so the calls over [first_cell, first_cell +
  * n_cells) of any partition concatenate to the whole list bit for bit (n_cells = -1: every cell from first_cell on).
+ * Random numbers: Philox4x32-10, key = seed (low word, high word), counter = (cell low, cell high, round, lane) with
+ * 64 lanes per round. Words 0-1 give the lane's gap -log(U(word 0, word 1)) / lam_max (U: the 53-bit uniform of
+ * crimp_timing_mcmc), words 2-3 the thinning uniform u = U(word 2, word 3). A round's 64 gaps are summed by an
+ * inclusive scan in doubling order (distances 1, 2, ..., 32) onto the running time, which starts at 0 in every cell;
+ * a candidate at s = cell * cell_s + that sum counts while s < min((cell + 1) * cell_s, span_s), survives inside the
+ * GTIs when u lam_max < S + bkg, and rounds follow until the running time passes the cell's end
+ * (tests/stream_reference.py replays it; tests/test_gpu_simulate_replay.py holds every candidate to the replay).
  *   t_out == NULL: the count pass alone, *n_out = the number of events. Otherwise cap < that number fails with
  *   CRIMP_ERR_ARG (nothing written, *n_out still set); else t_out[n] non-decreasing = out_offset_s + seconds since
  *   mjd_start, or the MJD mjd_start + s / 86400 with CRIMP_FLAG_TIME_DAYS; bkg_out[n] (may be NULL) = 1 for a
