@@ -102,7 +102,7 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
            "crimp_gather_ranges", "crimp_sim_events", "crimp_binary_delay", "crimp_photon_tile", "crimp_photon_nll",
-           "crimp_photon_mcmc", "crimp_orbit_nll", "crimp_orbit_mcmc")
+           "crimp_photon_mcmc", "crimp_orbit_nll", "crimp_orbit_mcmc", "crimp_orbit_search", "crimp_orbit_search_plan")
 
 _lib = None
 _lock = threading.Lock()
@@ -151,6 +151,9 @@ def load(require_device=True):
             L.crimp_orbit_nll.argtypes = [P, P, P, P, i64, MP, MP, MP, FP, P, i64, P, P, u32, P]
             L.crimp_orbit_mcmc.argtypes = [P, P, P, P, i64, MP, MP, MP, FP, P, P, P, i32, i64, ctypes.c_uint64, i64, P, P,
                                            P, u32, P]
+            L.crimp_orbit_search.argtypes = [P, i64, MP, ctypes.c_double, P, i32, P, i64, P, i64, ctypes.c_double, i32, i32,
+                                             i64, i64, P, P, u32, P]
+            L.crimp_orbit_search_plan.argtypes = [i64, i64, i32, i32, i64, ctypes.POINTER(i64)]
             TP = ctypes.POINTER(Template)
             L.crimp_photon_tile.argtypes = []
             L.crimp_photon_nll.argtypes = [P, P, i64, MP, FP, TP, ctypes.c_double, i32, P, i64, P, P, u32, P]
@@ -206,6 +209,15 @@ def last_nufft_cells():
     b, r = ctypes.c_int64(0), ctypes.c_int64(0)
     L.crimp_last_nufft_cells(ctypes.byref(b), ctypes.byref(r))
     return int(b.value), int(r.value)
+
+
+def orbit_search_plan(n, nf, nharm, stat=STAT_Z2, norb=1):
+    """The plan crimp_orbit_search takes for these sizes under the scratch cap in force (crimp_orbit_search_plan):
+    {slice, nslices, J, batch, nbatches, part_bytes}."""
+    L = load(require_device=False)
+    out = (ctypes.c_int64 * 6)()
+    check(L.crimp_orbit_search_plan(int(n), int(nf), int(nharm), int(stat), int(norb), out))
+    return dict(zip(("slice", "nslices", "J", "batch", "nbatches", "part_bytes"), (int(v) for v in out)))
 
 
 def photon_tile():

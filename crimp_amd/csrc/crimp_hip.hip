@@ -3546,6 +3546,132 @@ extern "C" int crimp_orbit_mcmc(const double* t_mjd, const double* y, const doub
                                    seed, first_problem, chain, logprob, accepted, flags, stream);
 }
 
+// ---- orbit search (orbit_search.h; its finalize kernel takes the best trial as crimp_best does, so the header
+// follows BestCand)
+#include "orbit_search.h"
+
+extern "C" int crimp_orbit_search_plan(int64_t n, int64_t nf, int32_t nharm, int32_t stat, int64_t norb, int64_t* out) {
+    ARGCHK(out != nullptr, "null argument");
+    ARGCHK(n >= 1 && nf >= 1 && norb >= 1, "n, nf, norb < 1");
+    ARGCHK(nharm >= 1 && nharm <= kOsMaxHarm, "nharm outside [1, 256]");
+    ARGCHK(stat == CRIMP_STAT_Z2 || stat == CRIMP_STAT_H, "stat must be CRIMP_STAT_Z2 or CRIMP_STAT_H");
+    const OrbitSearchPlan P = plan_orbit_search(n, nf, nharm, stat, norb, os_cap_from_env());
+    out[0] = P.slice;
+    out[1] = P.nslices;
+    out[2] = P.J;
+    out[3] = P.batch;
+    out[4] = P.nbatches;
+    out[5] = P.part_elems < 0 ? -1 : P.part_elems * 8;
+    return CRIMP_OK;
+}
+
+template <bool TWOD>
+static void launch_orbit_search(int J, dim3 grid, hipStream_t s, const double* t, int64_t n, const OSArgs& A,
+                                const double* orbits, const double* freq, int64_t nf, double* part) {
+    switch (J) {
+        case 2: k_orbit_search<2, TWOD><<<grid, kOsBlock, 0, s>>>(t, n, A, orbits, freq, nf, part); break;
+        case 4: k_orbit_search<4, TWOD><<<grid, kOsBlock, 0, s>>>(t, n, A, orbits, freq, nf, part); break;
+        case 8: k_orbit_search<8, TWOD><<<grid, kOsBlock, 0, s>>>(t, n, A, orbits, freq, nf, part); break;
+        default: k_orbit_search<16, TWOD><<<grid, kOsBlock, 0, s>>>(t, n, A, orbits, freq, nf, part); break;
+    }
+}
+
+extern "C" int crimp_orbit_search(const double* t_mjd, int64_t n, const crimp_timing_model* base, double tref_mjd,
+                                  const int32_t* keys, int32_t nkeys, const double* orbits, int64_t norb,
+                                  const double* freq, int64_t nf, double fdot, int32_t nharm, int32_t stat,
+                                  int64_t first, int64_t count, double* power, double* best, uint32_t flags,
+                                  void* stream) {
+    ARGCHK(n >= 1, "n < 1");
+    ARGCHK(nf >= 0 && norb >= 0, "nf or norb < 0");
+    ARGCHK(first >= 0 && count >= 0 && first <= norb && count <= norb - first, "orbit range outside [0, norb]");
+    ARGCHK(nharm >= 1 && nharm <= kOsMaxHarm, "nharm outside [1, 256]");
+    ARGCHK(stat == CRIMP_STAT_Z2 || stat == CRIMP_STAT_H, "stat must be CRIMP_STAT_Z2 or CRIMP_STAT_H");
+    ARGCHK(nkeys >= 0 && nkeys <= kOsMaxKeys, "nkeys outside [0, 11]");
+    ARGCHK(base != nullptr && t_mjd != nullptr && (keys != nullptr || nkeys == 0), "null argument");
+    ARGCHK(base->binary == CRIMP_BINARY_BT || base->binary == CRIMP_BINARY_ELL1, "the model has no binary");
+    ARGCHK(std::isfinite(tref_mjd) && std::isfinite(fdot), "tref or fdot is not finite");
+    OSArgs A{};
+    A.base.kind = base->binary;
+    {
+        double* r = A.base.raw;
+        r[CRIMP_ORBIT_PB] = base->bin_pb;
+        r[CRIMP_ORBIT_A1] = base->bin_a1;
+        r[CRIMP_ORBIT_T0] = base->bin_t0;
+        r[CRIMP_ORBIT_ECC] = base->bin_ecc;
+        r[CRIMP_ORBIT_OM] = base->bin_om;
+        r[CRIMP_ORBIT_OMDOT] = base->bin_omdot;
+        r[CRIMP_ORBIT_GAMMA] = base->bin_gamma;
+        r[CRIMP_ORBIT_EPS1] = base->bin_eps1;
+        r[CRIMP_ORBIT_EPS2] = base->bin_eps2;
+        r[CRIMP_ORBIT_PBDOT] = base->bin_pbdot;
+        r[CRIMP_ORBIT_A1DOT] = base->bin_a1dot;
+    }
+    for (int k = 0; k < kOfFields; ++k) A.col[k] = -1;
+    constexpr uint32_t bt_only = 1u << CRIMP_ORBIT_ECC | 1u << CRIMP_ORBIT_OM | 1u << CRIMP_ORBIT_OMDOT |
+                                 1u << CRIMP_ORBIT_GAMMA;
+    constexpr uint32_t ell1_only = 1u << CRIMP_ORBIT_EPS1 | 1u << CRIMP_ORBIT_EPS2;
+    for (int q = 0; q < nkeys; ++q) {
+        const int k = keys[q];
+        ARGCHK(k >= 0 && k < kOfFields, "key " + std::to_string(q) + " is not a CRIMP_ORBIT_* field");
+        ARGCHK(A.col[k] < 0, "two keys name one orbit field");
+        ARGCHK(!((1u << k) & (base->binary == CRIMP_BINARY_BT ? ell1_only : bt_only)),
+               "key names an orbit field the model's kind does not have");
+        A.col[k] = q;
+    }
+    A.nkeys = nkeys;
+    A.tref = tref_mjd;
+    A.c2 = 0.5 * fdot;
+    A.nharm = nharm;
+    if (count == 0 || nf == 0) return CRIMP_OK;
+    ARGCHK(freq != nullptr && (orbits != nullptr || nkeys == 0) && (power != nullptr || best != nullptr),
+           "null argument");
+    for (int64_t j = 0; j < nf; ++j) ARGCHK(std::isfinite(freq[j]), "a trial frequency is not finite");
+    // every orbit of the range against the limits of crimp_binary_delay, before anything is launched
+    for (int64_t o = first; o < first + count; ++o) {
+        double raw[kOfFields];
+        for (int k = 0; k < kOfFields; ++k) raw[k] = A.col[k] >= 0 ? orbits[o * nkeys + A.col[k]] : A.base.raw[k];
+        if (const char* why = os_orbit_fault(A.base.kind, raw))
+            return set_err(CRIMP_ERR_ARG, "orbit " + std::to_string(o) + ": " + why);
+    }
+    const Call call(flags, stream);
+    const bool dev = call.dev;
+    hipStream_t s = call.s;
+    const OrbitSearchPlan P = plan_orbit_search(n, nf, nharm, stat, count, os_cap_from_env());
+    ARGCHK(P.part_elems > 0 && P.nslices <= 0x7fffffff, "orbit search: the partial sums of one orbit do not fit");
+    const bool twod = fdot != 0.0;
+    {
+        Scratch sc(s);
+        const double *dt = nullptr, *dfreq = nullptr, *dorb = nullptr;
+        double *dpow = nullptr, *dbest = nullptr, *part = nullptr;
+        HIPCHK(stage_in(sc, t_mjd, (size_t)n, dev, &dt));
+        HIPCHK(stage_in(sc, freq, (size_t)nf, false, &dfreq));
+        if (nkeys > 0) HIPCHK(stage_in(sc, orbits + first * nkeys, (size_t)(count * nkeys), false, &dorb));
+        HIPCHK(stage_out(sc, power, (size_t)(count * nf), dev, &dpow));
+        HIPCHK(stage_out(sc, best, (size_t)(2 * count), dev, &dbest));
+        HIPCHK(sc.alloc(&part, (size_t)P.part_elems));
+        KernelTimer kt(s, call.timed);
+        kt.start();
+        for (int64_t b0 = 0; b0 < count; b0 += P.batch) {
+            const int64_t ob = std::min<int64_t>(P.batch, count - b0);
+            const dim3 grid((unsigned)P.nslices, (unsigned)ob);
+            const double* borb = dorb ? dorb + b0 * nkeys : nullptr;
+            if (twod)
+                launch_orbit_search<true>(P.J, grid, s, dt, n, A, borb, dfreq, nf, part);
+            else
+                launch_orbit_search<false>(P.J, grid, s, dt, n, A, borb, dfreq, nf, part);
+            HIPCHK(hipGetLastError());
+            k_orbit_search_finalize<<<(unsigned)ob, 256, 0, s>>>(part, ob, P.nslices, nf, nharm, stat, (double)n,
+                                                                 dpow ? dpow + b0 * nf : nullptr,
+                                                                 dbest ? dbest + 2 * b0 : nullptr);
+            HIPCHK(hipGetLastError());
+        }
+        kt.stop();
+        HIPCHK(copy_back(s, power, dpow, (size_t)(count * nf), dev));
+        HIPCHK(copy_back(s, best, dbest, (size_t)(2 * count), dev));
+    }
+    return finish(s, flags);
+}
+
 // ---- photon-domain timing fits (photon_fit.h)
 // What both calls hold after their one prologue: the plan's launch shape, the photon fit model, its map and the template
 struct PFCall {

@@ -597,6 +597,71 @@ def orbit_mcmc(t, y, yerr, pars, fit_bases, wave_bases, fmap, p0, lo, hi, steps,
                      flags)
 
 
+def orbit_keys(keys, kind):
+    """CRIMP_ORBIT_* indices of the orbit keys ``keys`` (PB, A1, T0 | TASC, ECC | E, OM, OMDOT, GAMMA, EPS1, EPS2,
+    PBDOT, A1DOT | XDOT) for a model of ``kind`` (N.BINARY_BT | N.BINARY_ELL1). ValueError for a name that is no orbit
+    key, a key named twice, or a key the kind does not have (T0, ECC, OM, OMDOT, GAMMA under ELL1; TASC, EPS1, EPS2
+    under BT)."""
+    keys = list(keys)
+    if len(keys) > len(N.ORBIT_FIELDS):
+        raise ValueError("at most %d orbit keys, got %d" % (len(N.ORBIT_FIELDS), len(keys)))
+    bt = kind == N.BINARY_BT
+    refused = ("TASC", "EPS1", "EPS2") if bt else ("T0", "ECC", "E", "OM", "OMDOT", "GAMMA")
+    out = []
+    for k in keys:
+        name = _ORBIT_ALIASES.get(str(k).upper(), str(k).upper())
+        if name not in N.ORBIT_FIELDS:
+            raise ValueError("%r is not an orbit key (%s, TASC, E, XDOT)" % (k, ", ".join(N.ORBIT_FIELDS)))
+        if str(k).upper() in refused:
+            raise ValueError("%s is not a key of a %s orbit" % (k, "BT" if bt else "ELL1"))
+        idx = N.ORBIT_FIELDS.index(name)
+        if idx in out:
+            raise ValueError("orbit key %s is named twice" % k)
+        out.append(idx)
+    return out
+
+
+def orbit_search(t_mjd, base, keys, orbits, freq, nharm, stat, fdot=0.0, tref=None, first=0, count=None, power=None,
+                 best=None, want_power=True, want_best=False, flags=0):
+    """Z^2 / H over a grid of orbits (crimp_orbit_search): (power [count, nf] or None, best [count, 2] or None; best is
+    [0, 2] when nf == 0).
+    ``base``: the timing-model dict (or a packed N.TimingModel) with the BINARY block; ``keys``: orbit key names (or
+    CRIMP_ORBIT_* indices); ``orbits`` [norb, nkeys]: absolute values in the .par's units, host memory; ``freq``: host
+    memory; ``t_mjd``: a NumPy array or a torch CUDA tensor (the results then stay on its device). Orbits
+    [first, first + count) are computed. ``tref`` defaults to (t[0] + t[-1]) / 2."""
+    m = base if isinstance(base, N.TimingModel) else _modeltm(base)
+    if m.binary == N.BINARY_NONE:
+        raise ValueError("the timing model has no BINARY")
+    kidx = [int(k) for k in keys] if all(isinstance(k, (int, np.integer)) for k in keys) else orbit_keys(keys, m.binary)
+    orbits = np.ascontiguousarray(np.asarray(orbits, dtype=np.float64).reshape(-1, len(kidx)) if len(kidx)
+                                  else np.zeros((np.shape(orbits)[0], 0)))
+    freq = np.ascontiguousarray(np.atleast_1d(np.asarray(freq, dtype=np.float64)).ravel())
+    norb, nf = orbits.shape[0], freq.size
+    if count is None:
+        count = norb - first
+    L = N.load()
+    b = N.Buffers()
+    tp = b.arg(t_mjd, np.float64)
+    n = int(t_mjd.numel() if N._is_torch(t_mjd) else np.size(t_mjd))
+    if tref is None:
+        flat = t_mjd.reshape(-1)
+        tref = float((flat[0] + flat[-1]).item()) / 2 if N._is_torch(t_mjd) else (flat[0] + flat[-1]) / 2
+    if power is None and want_power:
+        power = _empty_like_input(t_mjd, max(count, 0) * nf, b).reshape(max(count, 0), nf)
+    if best is None and want_best:
+        # (no trial, no best: nf == 0 gives an empty table)
+        best = _empty_like_input(t_mjd, (max(count, 0) if nf else 0) * 2, b).reshape(max(count, 0) if nf else 0, 2)
+    pp = b.arg(power, np.float64, writable=True) if power is not None else None
+    bp = b.arg(best, np.float64, writable=True) if best is not None else None
+    karr = np.asarray(kidx, dtype=np.int32)
+    with b.device_guard():
+        N.check(L.crimp_orbit_search(tp, n, ctypes.byref(m), float(tref), ctypes.c_void_p(karr.ctypes.data),
+                                     len(kidx), ctypes.c_void_p(orbits.ctypes.data), norb,
+                                     ctypes.c_void_p(freq.ctypes.data), nf, float(fdot), int(nharm), int(stat),
+                                     int(first), int(count), pp, bp, b.flags(flags), b.stream()))
+    return power, best
+
+
 def _photon_args(b, t, x, par, phoff):
     n = int(t.numel() if N._is_torch(t) else np.size(t))
     if int(x.numel() if N._is_torch(x) else np.size(x)) != n:

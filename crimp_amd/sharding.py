@@ -7,6 +7,8 @@ ranks, one collective per search.
                        per-trial powers (``gather='all'``, every rank gets the full array) or one
                        ``all_gather`` of each rank's best (power, index) (``gather='best'``);
                        ties resolve to the lowest flat index, as ``np.argmax`` does;
+* ``sharded_orbit_search``  each rank computes a contiguous slice of the orbit grid through
+                       ``crimp_orbit_search`` (first/count); one ``all_gather`` of the (orbit, trial) powers;
 * ``sharded_toa_fit``  each rank fits a contiguous block of intervals, loading only their photons
                        (``interval_shard``: blocks cut at quantiles of the intervals' photon counts, a fit's cost
                        being photon-proportional, plus a fixed per-interval share); one ``all_gather`` of the
@@ -141,6 +143,40 @@ def sharded_search(time, freq, nharm=2, stat=0, freq_dot=None, gather="all", com
     if as_tensor:
         return out.to(time.device)
     return out.cpu().numpy()
+
+
+def sharded_orbit_search(time_mjd, base, keys, orbits, freq, nharm=2, stat=0, fdot=0.0, tref=None, compute=None,
+                         flags=0):
+    """Z^2 (stat=0) / H (stat=1) of every (orbit, trial frequency), the orbit axis sharded across the process group:
+    the (norb, nf) powers, identical on every rank (a tensor on the rank's device when ``time_mjd`` is a device
+    tensor, else a numpy array). The arguments are those of ``ops.orbit_search``; a power does not depend on the
+    slice its orbit is computed in. ``tref`` defaults to (time[0] + time[-1]) / 2, shared by every shard."""
+    import torch
+    dist, world, rank = _dist()
+    as_tensor = isinstance(time_mjd, torch.Tensor)
+    if tref is None:
+        tref = float((time_mjd[0] + time_mjd[-1]).item()) / 2 if as_tensor else (time_mjd[0] + time_mjd[-1]) / 2
+    orbits = np.asarray(orbits, dtype=np.float64)
+    orbits = orbits.reshape(orbits.shape[0], -1)
+    norb, nf = orbits.shape[0], int(np.size(freq))
+    first, count = shard_range(norb, world, rank)
+    if compute is None:
+        from . import ops
+        local = ops.orbit_search(time_mjd, base, keys, orbits, freq, nharm, stat, fdot=fdot, tref=tref, first=first,
+                                 count=count, flags=flags)[0]
+    else:
+        local = compute(time_mjd, base, keys, orbits, freq, nharm, stat, fdot, tref, first, count)
+    if dist is None:
+        return local
+    dev = _device_for_backend(dist)
+    width = shard_range(norb, world, 0)[1]
+    buf = torch.full((width, nf), np.nan, dtype=torch.float64, device=dev)
+    buf[:count] = _as_comm(local, dev).reshape(count, nf)
+    allp = torch.empty((world * width, nf), dtype=torch.float64, device=dev)
+    dist.all_gather_into_tensor(allp, buf)
+    allp = allp.reshape(world, width, nf)
+    out = torch.cat([allp[r, :shard_range(norb, world, r)[1]] for r in range(world)])
+    return out.to(time_mjd.device) if as_tensor else out.cpu().numpy()
 
 
 # A fit's cost per interval in photon units beyond its photons: the workgroup's fixed passes and reductions (config 5:

@@ -432,6 +432,35 @@ int crimp_orbit_mcmc(const double* t_mjd, const double* y, const double* yerr, c
                      int64_t first_problem, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
                      void* stream);
 
+/* ---- orbit search: Z^2_m / H over a grid of binary orbits (not in the reference)
+ * For orbit o of orbits[norb][nkeys] (host, row-major): B_o is base's orbit with field keys[q] (CRIMP_ORBIT_*, each
+ * at most once, valid for base's kind) replaced by orbits[o][q], an absolute value in the unit of crimp_timing_model's
+ * binary block; derived as crimp_binary_delay derives base's. With tau = the delay crimp_binary_delay defines,
+ *   dt_i = fl(fl((t_i - tref_mjd) 86400) - tau_{B_o}(t_i)),   ph = freq[j] dt + (0.5 fdot) dt^2   (cycles)
+ *   power[o - first][j] = Z^2_nharm (CRIMP_STAT_Z2) or H (CRIMP_STAT_H) of C_k = sum_i cos 2 pi k ph, S_k (sin), n,
+ * in the formula order of crimp_search's fp64 path, for orbits [first, first + count). best[o - first] = (the largest
+ * power of the row, its trial index as a double), np.argmax semantics (the lowest index wins a tie, a NaN wins). power
+ * or best may be NULL (not both unless count or nf is 0). base's spin keys are not read. A photon whose delay
+ * iteration reaches its cap makes its orbit's powers NaN.
+ * power[o][j] does not depend on norb, first, count or the scratch cap: the photons are summed in an order fixed by n.
+ * t_mjd, power and best follow CRIMP_FLAG_DEVICE_PTRS; base, keys, orbits and freq are host pointers always.
+ * CRIMP_FLAG_TIME_KERNELS times the search and finalize kernels together (crimp_last_kernel_ms). count == 0 or
+ * nf == 0 launches nothing. Partial sums of a launch are bounded by CRIMP_ORBIT_SCRATCH_KB (default 1 GiB): more
+ * orbits run in batches.
+ * CRIMP_ERR_ARG, nothing launched or written: n < 1; nf, norb < 0; [first, first + count) outside [0, norb]; nharm
+ * outside [1, 256]; stat; nkeys outside [0, 11]; "key ... is not a CRIMP_ORBIT_* field", "two keys name one orbit
+ * field", "key names an orbit field the model's kind does not have"; "the model has no binary"; a non-finite freq,
+ * fdot or tref; and "orbit <index>: <text>" for the first orbit of the range outside the limits of
+ * crimp_binary_delay (its texts). */
+int crimp_orbit_search(const double* t_mjd, int64_t n, const crimp_timing_model* base, double tref_mjd,
+                       const int32_t* keys, int32_t nkeys, const double* orbits, int64_t norb, const double* freq,
+                       int64_t nf, double fdot, int32_t nharm, int32_t stat, int64_t first, int64_t count,
+                       double* power, double* best, uint32_t flags, void* stream);
+
+/* The plan crimp_orbit_search takes for these sizes under the scratch cap in force (no device needed):
+ * out[0..5] = photons per slice, slices, trials per chunk J, orbits per launch, launches, bytes of partial sums. */
+int crimp_orbit_search_plan(int64_t n, int64_t nf, int32_t nharm, int32_t stat, int64_t norb, int64_t* out);
+
 /* Photon-domain timing fits (not in the reference; csrc/photon_fit.h).
  *
  * The vector p corrects the model as inject_free_params does, full(p) = par - p on every free key, and its likelihood
