@@ -102,7 +102,8 @@ EXPORTS = ("crimp_version", "crimp_last_error", "crimp_last_kernel_ms", "crimp_l
            "crimp_toa_grid", "crimp_toa_fit", "crimp_toa_redchi2", "crimp_toa_fit_redchi2", "crimp_toa_shape_points", "crimp_binphases",
            "crimp_phase_cube", "crimp_timing_nll", "crimp_timing_mcmc", "crimp_is_sorted", "crimp_select_intervals",
            "crimp_gather_ranges", "crimp_sim_events", "crimp_binary_delay", "crimp_photon_tile", "crimp_photon_nll",
-           "crimp_photon_mcmc", "crimp_orbit_nll", "crimp_orbit_mcmc", "crimp_orbit_search", "crimp_orbit_search_plan")
+           "crimp_photon_mcmc", "crimp_orbit_nll", "crimp_orbit_mcmc", "crimp_orbit_search", "crimp_orbit_search_plan",
+           "crimp_photon_orbit_nll", "crimp_photon_orbit_mcmc")
 
 _lib = None
 _lock = threading.Lock()
@@ -159,6 +160,8 @@ def load(require_device=True):
             L.crimp_photon_nll.argtypes = [P, P, i64, MP, FP, TP, ctypes.c_double, i32, P, i64, P, P, u32, P]
             L.crimp_photon_mcmc.argtypes = [P, P, i64, MP, FP, TP, ctypes.c_double, i32, P, P, P, i32, i64,
                                             ctypes.c_uint64, P, P, P, u32, P]
+            L.crimp_photon_orbit_nll.argtypes = L.crimp_photon_nll.argtypes
+            L.crimp_photon_orbit_mcmc.argtypes = L.crimp_photon_mcmc.argtypes
             L.crimp_is_sorted.argtypes = [P, i64, ctypes.POINTER(i32), u32, P]
             L.crimp_select_intervals.argtypes = [P, i64, P, P, i64, P, P, P, u32, P]
             L.crimp_gather_ranges.argtypes = [P, i64, P, P, i64, P, u32, P]

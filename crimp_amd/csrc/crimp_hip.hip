@@ -1652,6 +1652,7 @@ __global__ __launch_bounds__(kFixBlock) void k_search_f64_few(
 #include "orbit_fit.h"
 #include "sim_events.h"
 #include "photon_fit.h"
+#include "photon_orbit_fit.h"
 
 // ============================================================== 6. C-ABI
 // A second stream per device for crimp_toa_fit's overlapped halves (created once, kept for the process)
@@ -3672,21 +3673,28 @@ extern "C" int crimp_orbit_search(const double* t_mjd, int64_t n, const crimp_ti
     return finish(s, flags);
 }
 
-// ---- photon-domain timing fits (photon_fit.h)
-// What both calls hold after their one prologue: the plan's launch shape, the photon fit model, its map and the template
+// ---- photon-domain timing fits (photon_fit.h), binary-free or under an orbit (photon_orbit_fit.h)
+// What a call holds after its one prologue: the plan's launch shape, the photon fit model, its map and the template;
+// the orbit's calls also par's orbit and par's spin model (the prologue kernel's rates)
 struct PFCall {
     PFLaunch L;
     CPModel base;
     PFMap map;
     TplDev T;
+    bool orbit = false;
+    POFOrbit ob;
+    CPModel parm;
 };
 
-// every check of crimp_photon_nll / _mcmc that does not need the device, and the host plan (photon_fit_plan.h)
+// every check of a call that does not need the device, and the host plan (photon_fit_plan.h; orbit: the two
+// crimp_photon_orbit_* calls, photon_orbit_fit_plan.h)
 static int pf_prologue(int64_t n, const crimp_timing_model* par, const crimp_fit_map* map, const crimp_template* tpl,
-                       double norm, int32_t phoff, int64_t P, PFCall* c) {
+                       double norm, int32_t phoff, int64_t P, bool orbit, PFCall* c) {
     crimp_timing_model fit;
     int32_t parts = 0, nterms = 1;
-    if (const char* e = plan_photon_model(par, map, phoff, &fit, &c->map, &parts, &nterms))
+    c->orbit = orbit;
+    if (const char* e = orbit ? plan_photon_orbit_model(par, map, phoff, &fit, &c->map, &parts, &nterms, &c->ob)
+                              : plan_photon_model(par, map, phoff, &fit, &c->map, &parts, &nterms))
         return set_err(CRIMP_ERR_ARG, e);
     if (const int rc = make_tpl(tpl, &c->T)) return rc;
     ARGCHK(std::isfinite(norm) && norm > 0.0, "norm must be positive");
@@ -3694,18 +3702,28 @@ static int pf_prologue(int64_t n, const crimp_timing_model* par, const crimp_fit
     make_cpmodel(&fit, parts, &c->base);
     c->base.nterms = nterms;
     c->base.f0 = 1.0;  // the wave coefficients carry F0 (photon_wave_coef)
+    if (orbit) make_cpmodel(par, 7, &c->parm);
     return CRIMP_OK;
 }
 
-// the device copies every launch of a call reads
+// the device copies every launch of a call reads; the orbit's calls also the room of the per-photon constants
 struct PFDev {
     CPModel* base = nullptr;
     PFMap* map = nullptr;
     TplDev* T = nullptr;
     double2* tab = nullptr;
     double *psum = nullptr, *pmin = nullptr;
+    CPModel* parm = nullptr;
+    double* consts = nullptr;  // [3][n]: tau0, nu, nud
 };
-static int pf_upload(Scratch& sc, hipStream_t s, const PFCall& c, PFDev* d) {
+static int pf_upload(Scratch& sc, hipStream_t s, const PFCall& c, int64_t n, PFDev* d) {
+    if (c.orbit) {
+        HIPCHK(sc.alloc(&d->parm, 1));
+        HIPCHK(sc.alloc(&d->consts, 3 * (size_t)n));
+        HIPCHK(h2d(d->parm, &c.parm, sizeof(CPModel)));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_photon_orbit_nll),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(POFLds)));
+    }
     HIPCHK(sc.alloc(&d->base, 1));
     HIPCHK(sc.alloc(&d->map, 1));
     HIPCHK(sc.alloc(&d->T, 1));
@@ -3724,13 +3742,35 @@ static int pf_upload(Scratch& sc, hipStream_t s, const PFCall& c, PFDev* d) {
 
 extern "C" int crimp_photon_tile(void) { return kPfTile; }
 
-extern "C" int crimp_photon_nll(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
-                                const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
-                                const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags,
-                                void* stream) {
+// the orbit's per-photon constants, once per call (nothing for a binary-free call); part of a call's timed cost
+static void pf_launch_prologue(hipStream_t s, const PFCall& c, const PFDev& d, const double* dt, int64_t n) {
+    if (c.orbit)
+        k_photon_orbit_prologue<<<(unsigned)std::min<int64_t>(cdiv(n, 256), int64_t(1) << 20), 256, 0, s>>>(
+            dt, n, c.ob, d.parm, d.consts);
+}
+
+// the likelihood kernel of a call on P vectors: (sum ln m, min m) pairs into d.psum / d.pmin
+static void pf_launch_nll(hipStream_t s, const PFCall& c, const PFDev& d, const double* dt, const double* dx,
+                          int64_t n, double norm, const double* pvec, const int32_t* active, int64_t P,
+                          double* delta) {
+    const dim3 grid((unsigned)c.L.tiles, (unsigned)cdiv(P, kPfWaves));
+    if (c.orbit)
+        k_photon_orbit_nll<<<grid, kPfWaves * 64, sizeof(POFLds), s>>>(dt, dx, d.consts, n, d.base, c.ob, d.map, d.T,
+                                                                      d.tab, norm, pvec, active, P, d.psum, d.pmin,
+                                                                      delta);
+    else
+        k_photon_nll<<<grid, kPfWaves * 64, sizeof(PFLds), s>>>(dt, dx, n, d.base, d.map, d.T, d.tab, norm, pvec,
+                                                                active, P, d.psum, d.pmin, delta);
+}
+
+// crimp_photon_nll and (orbit) crimp_photon_orbit_nll
+static int photon_nll_call(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                           const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                           const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags, void* stream,
+                           bool orbit) {
     ARGCHK(t_mjd != nullptr && x != nullptr && pvec != nullptr && nll != nullptr, "null argument");
     PFCall c;
-    if (const int rc = pf_prologue(n, par, map, tpl, norm, phoff, P, &c)) return rc;
+    if (const int rc = pf_prologue(n, par, map, tpl, norm, phoff, P, orbit, &c)) return rc;
     const Call call(flags, stream);
     const bool dev = call.dev;
     hipStream_t s = call.s;
@@ -3745,11 +3785,11 @@ extern "C" int crimp_photon_nll(const double* t_mjd, const double* x, int64_t n,
         HIPCHK(stage_in(sc, pvec, (size_t)P * D, dev, &dp));
         HIPCHK(stage_out(sc, nll, (size_t)P, dev, &dnll));
         HIPCHK(stage_out(sc, delta, (size_t)P * (size_t)n, dev, &ddel));
-        if (const int rc = pf_upload(sc, s, c, &d)) return rc;
+        if (const int rc = pf_upload(sc, s, c, n, &d)) return rc;
         KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
         kt.start();
-        k_photon_nll<<<dim3((unsigned)c.L.tiles, (unsigned)c.L.groups), kPfWaves * 64, sizeof(PFLds), s>>>(
-            dt, dx, n, d.base, d.map, d.T, d.tab, norm, dp, nullptr, P, d.psum, d.pmin, ddel);
+        pf_launch_prologue(s, c, d, dt, n);
+        pf_launch_nll(s, c, d, dt, dx, n, norm, dp, nullptr, P, ddel);
         HIPCHK(hipGetLastError());
         k_photon_reduce<<<(unsigned)cdiv(P, 4), 256, 0, s>>>(d.psum, d.pmin, c.L.tiles, n, norm, P, dnll);
         HIPCHK(hipGetLastError());
@@ -3760,15 +3800,30 @@ extern "C" int crimp_photon_nll(const double* t_mjd, const double* x, int64_t n,
     return finish(s, flags);
 }
 
-extern "C" int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
-                                 const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
-                                 const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps,
-                                 uint64_t seed, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
-                                 void* stream) {
+extern "C" int crimp_photon_nll(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                                const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                                const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags,
+                                void* stream) {
+    return photon_nll_call(t_mjd, x, n, par, map, tpl, norm, phoff, pvec, P, nll, delta, flags, stream, false);
+}
+
+extern "C" int crimp_photon_orbit_nll(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                                      const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                                      const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags,
+                                      void* stream) {
+    return photon_nll_call(t_mjd, x, n, par, map, tpl, norm, phoff, pvec, P, nll, delta, flags, stream, true);
+}
+
+// crimp_photon_mcmc and (orbit) crimp_photon_orbit_mcmc
+static int photon_mcmc_call(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                            const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                            const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps,
+                            uint64_t seed, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
+                            void* stream, bool orbit) {
     ARGCHK(t_mjd != nullptr && x != nullptr && p0 != nullptr && lo != nullptr && hi != nullptr && chain != nullptr &&
                logprob != nullptr && accepted != nullptr, "null argument");
     PFCall c;
-    if (const int rc = pf_prologue(n, par, map, tpl, norm, phoff, W >= 1 ? W : 1, &c)) return rc;
+    if (const int rc = pf_prologue(n, par, map, tpl, norm, phoff, W >= 1 ? W : 1, orbit, &c)) return rc;
     const int32_t D = c.map.ndim + c.map.phoff;
     ARGCHK(W >= 2 && W % 2 == 0 && W <= 256 && W >= 2 * D, "walkers: even, >= 2 ndim and <= 256");
     ARGCHK(steps >= 1 && steps <= (int64_t(1) << 31), "steps out of range");
@@ -3789,7 +3844,7 @@ extern "C" int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n
         HIPCHK(stage_out(sc, chain, rows * nd, dev, &A.chain));
         HIPCHK(stage_out(sc, logprob, rows, dev, &A.logprob));
         HIPCHK(stage_out(sc, accepted, w, dev, &A.accepted));
-        if (const int rc = pf_upload(sc, s, c, &d)) return rc;
+        if (const int rc = pf_upload(sc, s, c, n, &d)) return rc;
         HIPCHK(sc.alloc(&A.pos, w * nd));
         HIPCHK(sc.alloc(&A.lp, w));
         HIPCHK(sc.alloc(&A.nacc, w));
@@ -3804,20 +3859,18 @@ extern "C" int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n
         A.W = W;
         A.D = D;
         A.seed = seed;
-        const unsigned tiles = (unsigned)c.L.tiles;
         const int64_t half = W / 2;
         KernelTimer kt(s, flags & CRIMP_FLAG_TIME_KERNELS);
         kt.start();
         // the whole chain is queued here; the host waits once, in finish()
+        pf_launch_prologue(s, c, d, dt, n);
         k_photon_step<<<1, kPfStepWaves * 64, 0, s>>>(A, 0, 0, 0, 0);
-        k_photon_nll<<<dim3(tiles, (unsigned)cdiv(W, kPfWaves)), kPfWaves * 64, sizeof(PFLds), s>>>(
-            dt, dx, n, d.base, d.map, d.T, d.tab, norm, A.pos, A.act, W, d.psum, d.pmin, nullptr);
+        pf_launch_nll(s, c, d, dt, dx, n, norm, A.pos, A.act, W, nullptr);
         k_photon_step<<<1, kPfStepWaves * 64, 0, s>>>(A, 1, 0, 0, 0);
         HIPCHK(hipGetLastError());
         for (int64_t st = 0; st < steps; ++st)
             for (int h = 0; h < 2; ++h) {
-                k_photon_nll<<<dim3(tiles, (unsigned)cdiv(half, kPfWaves)), kPfWaves * 64, sizeof(PFLds), s>>>(
-                    dt, dx, n, d.base, d.map, d.T, d.tab, norm, A.prop, A.act, half, d.psum, d.pmin, nullptr);
+                pf_launch_nll(s, c, d, dt, dx, n, norm, A.prop, A.act, half, nullptr);
                 k_photon_step<<<1, kPfStepWaves * 64, 0, s>>>(A, 2, st, h, st + 1 == steps && h == 1);
             }
         HIPCHK(hipGetLastError());
@@ -3827,6 +3880,24 @@ extern "C" int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n
         HIPCHK(copy_back(s, accepted, A.accepted, w, dev));
     }
     return finish(s, flags);
+}
+
+extern "C" int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                                 const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                                 const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps,
+                                 uint64_t seed, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
+                                 void* stream) {
+    return photon_mcmc_call(t_mjd, x, n, par, map, tpl, norm, phoff, p0, lo, hi, W, steps, seed, chain, logprob,
+                            accepted, flags, stream, false);
+}
+
+extern "C" int crimp_photon_orbit_mcmc(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                                       const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                                       const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps,
+                                       uint64_t seed, double* chain, double* logprob, int64_t* accepted,
+                                       uint32_t flags, void* stream) {
+    return photon_mcmc_call(t_mjd, x, n, par, map, tpl, norm, phoff, p0, lo, hi, W, steps, seed, chain, logprob,
+                            accepted, flags, stream, true);
 }
 
 

@@ -57,12 +57,16 @@ inline const char* plan_photon_launch(int64_t n, int64_t P, PFLaunch* L) {
 // The photon fit model of (par, map, phoff): `fit` is what make_cpmodel takes, *parts and *nterms what the kernel
 // evaluates of it (Taylor terms up to the highest free Fn, glitches up to the last free one, waves when use_waves).
 // Returns the CRIMP_ERR_ARG text of a refusal, or nullptr. map->branch and map->f0_param are not read.
+// orbit_fields (plan_photon_orbit_model; else null): par may carry an orbit and CRIMP_FIT_SLOT_BINARY slots are
+// admitted; the mask of the orbit fields they name is returned there, and par's binary block is not read.
 inline const char* plan_photon_model(const crimp_timing_model* par, const crimp_fit_map* map, int32_t phoff,
-                                     crimp_timing_model* fit, PFMap* dm, int32_t* parts, int32_t* nterms) {
+                                     crimp_timing_model* fit, PFMap* dm, int32_t* parts, int32_t* nterms,
+                                     uint32_t* orbit_fields = nullptr) {
     if (par == nullptr || map == nullptr) return "null argument";
     if (phoff != 0 && phoff != 1) return "phoff must be 0 or 1";
     if (map->ndim < 1 || map->ndim > CRIMP_FIT_MAX_DIM - phoff) return "ndim must be 1..CRIMP_FIT_MAX_DIM - phoff";
-    if (par->binary != CRIMP_BINARY_NONE) return "binary models are not fitted yet";
+    if (orbit_fields == nullptr && par->binary != CRIMP_BINARY_NONE) return "binary models are not fitted yet";
+    if (orbit_fields) *orbit_fields = 0;
     if (par->n_glitch < 0 || par->n_glitch > CRIMP_MAX_GLITCH) return "n_glitch out of range";
     if (par->n_wave < 0 || par->n_wave > CRIMP_MAX_WAVE) return "n_wave out of range";
     std::memset(dm, 0, sizeof(*dm));
@@ -96,6 +100,11 @@ inline const char* plan_photon_model(const crimp_timing_model* par, const crimp_
             if (sl.index >= par->n_wave) return "slot names a wave harmonic outside the model";
             dm->wave_param[sl.index][sl.sub] = k;
             wave_free = true;
+        } else if (sl.kind == CRIMP_FIT_SLOT_BINARY && orbit_fields != nullptr) {
+            if (sl.index < 0 || sl.index > CRIMP_ORBIT_A1DOT)
+                return "slot names an orbit field outside CRIMP_ORBIT_PB..CRIMP_ORBIT_A1DOT";
+            if (*orbit_fields >> sl.index & 1u) return "two slots name one orbit field";
+            *orbit_fields |= 1u << sl.index;
         } else {
             return "unknown slot kind";
         }

@@ -83,6 +83,11 @@ class PhotonFit:
                               want_delta=True)
         return d[0] if p.ndim == 1 else d
 
+    def mcmc(self, p0, lo, hi, steps, seed):
+        """(chain [steps, W, D], logprob [steps, W], accepted [W]) of the device sampler on this problem."""
+        return ops.photon_mcmc(self.t, self.x, self.par, self.map, self.tpl, self.norm, p0, lo, hi, steps, seed,
+                               phoff=self.phoff)
+
     def full(self, pvec):
         """The full model of one vector: ``parfile``'s values with the correction applied (PHOFF is not a model key)."""
         p = np.asarray(pvec, dtype=float).reshape(-1)
@@ -118,8 +123,7 @@ def run_photon_mcmc(problem: PhotonFit, prior, steps: int = 10000, burn: int = 5
         p0[:, i] = rng.uniform(lo, hi, size=walkers)
     kernel_seed = int(rng.integers(0, 2 ** 63)) if seed is None else int(seed)
     lo, hi = prior_box(prior, keys)
-    chain, logprob, accepted = ops.photon_mcmc(problem.t, problem.x, problem.par, problem.map, problem.tpl,
-                                               problem.norm, p0, lo, hi, steps, kernel_seed, phoff=problem.phoff)
+    chain, logprob, accepted = problem.mcmc(p0, lo, hi, steps, kernel_seed)
     sampler = DeviceSampler(chain, logprob, accepted)
     if chain_npy:
         np.save(chain_npy, sampler.get_chain())

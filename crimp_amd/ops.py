@@ -662,12 +662,12 @@ def orbit_search(t_mjd, base, keys, orbits, freq, nharm, stat, fdot=0.0, tref=No
     return power, best
 
 
-def _photon_args(b, t, x, par, phoff):
+def _photon_args(b, t, x, par, phoff, orbit=False):
     n = int(t.numel() if N._is_torch(t) else np.size(t))
     if int(x.numel() if N._is_torch(x) else np.size(x)) != n:
         raise ValueError("t and x differ in length")
     m = par if isinstance(par, N.TimingModel) else _modeltm(par)
-    if m.binary:
+    if m.binary and not orbit:
         raise ValueError("binary models are not fitted yet")
     return b.arg(t, np.float64), b.arg(x, np.float64), n, m, 1 if phoff else 0
 
@@ -677,9 +677,20 @@ def photon_nll(t, x, par, fmap, tpl, norm, pvec, phoff=False, want_delta=False, 
     ``t``: photon MJDs; ``x``: their folded phases under ``par`` (cycles); ``par``: a timing-model dict or
     N.TimingModel; ``fmap``: ``fit_map`` of the free keys; ``pvec`` [P, D], D = ndim + 1 with ``phoff`` (PHOFF last).
     Returns nll [P], or (nll, delta [P, n]) with ``want_delta``."""
+    return _photon_nll(False, t, x, par, fmap, tpl, norm, pvec, phoff, want_delta, flags)
+
+
+def photon_orbit_nll(t, x, par, fmap, tpl, norm, pvec, phoff=False, want_delta=False, flags=0):
+    """``photon_nll`` for a model with an orbit (crimp_photon_orbit_nll): ``par`` carries its BINARY block, ``x`` is the
+    folded phase at the emission time, ``fmap`` an ``orbit_fit_map``. A vector whose corrected orbit is outside the
+    limits gives +inf and a delta row of +inf."""
+    return _photon_nll(True, t, x, par, fmap, tpl, norm, pvec, phoff, want_delta, flags)
+
+
+def _photon_nll(orbit, t, x, par, fmap, tpl, norm, pvec, phoff, want_delta, flags):
     L = N.load()
     b = N.Buffers()
-    tp, xp, n, m, ph = _photon_args(b, t, x, par, phoff)
+    tp, xp, n, m, ph = _photon_args(b, t, x, par, phoff, orbit)
     D = int(fmap.ndim) + ph
     tot = int(pvec.numel() if N._is_torch(pvec) else np.size(pvec))
     if tot == 0 or tot % D:
@@ -690,18 +701,29 @@ def photon_nll(t, x, par, fmap, tpl, norm, pvec, phoff=False, want_delta=False, 
     delta = _empty_like_input(t, P * n, b) if want_delta else None
     nllp = b.arg(nll, np.float64, writable=True)
     dp = b.arg(delta, np.float64, writable=True) if want_delta else None
+    call = L.crimp_photon_orbit_nll if orbit else L.crimp_photon_nll
     with b.device_guard():
-        N.check(L.crimp_photon_nll(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph,
-                                   pp, P, nllp, dp, b.flags(flags), b.stream()))
+        N.check(call(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph, pp, P, nllp,
+                     dp, b.flags(flags), b.stream()))
     return (nll, delta.reshape(P, n)) if want_delta else nll
 
 
 def photon_mcmc(t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff=False, flags=0):
     """The ensemble sampler of the photon likelihood (crimp_photon_mcmc): ``p0`` [W, D], ``lo`` / ``hi`` [D] (+-inf: no
     bound). Returns (chain [steps, W, D], logprob [steps, W], accepted [W]); placement follows ``t``."""
+    return _photon_mcmc(False, t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff, flags)
+
+
+def photon_orbit_mcmc(t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff=False, flags=0):
+    """``photon_mcmc`` for a model with an orbit (crimp_photon_orbit_mcmc); the arguments of ``photon_orbit_nll`` and
+    ``photon_mcmc``, the same outputs. No vector outside the orbit's limits enters the chain."""
+    return _photon_mcmc(True, t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff, flags)
+
+
+def _photon_mcmc(orbit, t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff, flags):
     L = N.load()
     b = N.Buffers()
-    tp, xp, n, m, ph = _photon_args(b, t, x, par, phoff)
+    tp, xp, n, m, ph = _photon_args(b, t, x, par, phoff, orbit)
     D = int(fmap.ndim) + ph
     shape = tuple(p0.shape)
     if len(shape) != 2 or shape[1] != D:
@@ -712,10 +734,10 @@ def photon_mcmc(t, x, par, fmap, tpl, norm, p0, lo, hi, steps, seed, phoff=False
             raise ValueError("lo and hi must be [%d]" % D)
     pp, lop, hip_ = b.arg(p0, np.float64), b.arg(lo, np.float64), b.arg(hi, np.float64)
     (chain, logprob, accepted), outp = _chain_outputs(b, t, 1, steps, W, D)
+    call = L.crimp_photon_orbit_mcmc if orbit else L.crimp_photon_mcmc
     with b.device_guard():
-        N.check(L.crimp_photon_mcmc(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph,
-                                    pp, lop, hip_, W, steps, int(seed) & 0xFFFFFFFFFFFFFFFF, *outp, b.flags(flags),
-                                    b.stream()))
+        N.check(call(tp, xp, n, ctypes.byref(m), ctypes.byref(fmap), ctypes.byref(tpl), float(norm), ph, pp, lop, hip_,
+                     W, steps, int(seed) & 0xFFFFFFFFFFFFFFFF, *outp, b.flags(flags), b.stream()))
     return chain.reshape(steps, W, D), logprob.reshape(steps, W), accepted
 
 

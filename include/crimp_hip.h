@@ -404,7 +404,7 @@ int crimp_timing_mcmc(const double* t_mjd, const double* y, const double* yerr, 
  * a base orbit outside the limits (the texts of crimp_binary_delay); "slot names an orbit field the model's kind does
  * not have" (ECC, OM, OMDOT, GAMMA under ELL1; EPS1, EPS2 under BT); "slot names an orbit field outside
  * CRIMP_ORBIT_PB..CRIMP_ORBIT_A1DOT"; "two slots name one orbit field". */
-#define CRIMP_FIT_SLOT_BINARY 3 /* index = CRIMP_ORBIT_* (crimp_orbit_nll / _mcmc only) */
+#define CRIMP_FIT_SLOT_BINARY 3 /* index = CRIMP_ORBIT_* (crimp_orbit_* and crimp_photon_orbit_* only) */
 #define CRIMP_ORBIT_PB 0
 #define CRIMP_ORBIT_A1 1
 #define CRIMP_ORBIT_T0 2 /* T0 (BT) or TASC (ELL1) */
@@ -497,6 +497,42 @@ int crimp_photon_mcmc(const double* t_mjd, const double* x, int64_t n, const cri
                       const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
                       const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps, uint64_t seed,
                       double* chain, double* logprob, int64_t* accepted, uint32_t flags, void* stream);
+
+/* Photon-domain timing fits under a binary orbit, the orbital keys free (not in the reference;
+ * csrc/photon_orbit_fit.h). crimp_photon_nll / _mcmc refuse a model with an orbit; these two calls take
+ * the same arguments with par carrying its binary block, and map may hold CRIMP_FIT_SLOT_BINARY slots, which correct
+ * par's orbit as in crimp_orbit_nll: field(p) = par's field - p in the unit of crimp_timing_model's binary block, the
+ * fp64 difference. With B0 the orbit of par, B(p) the corrected one and tau_B(t) the delay of crimp_binary_delay,
+ *   te0 = t - tau_B0(t) / 86400,   teF = t - tau_B(p)(t) / 86400,   dtau = tau_B(p)(t) - tau_B0(t)
+ *   delta_i = phi_pf(p)(teF_i) + R_i,   R_i = dtau_i (nu_i - nud_i dtau_i / 2)
+ *   u_i = x_i - delta_i - PHOFF,   NLL as crimp_photon_nll defines it,
+ * phi_pf(p) the photon fit model of crimp_photon_nll (every linear amplitude of par 0, the free ones their entries,
+ * the wave cross term exact) at the emission time of the corrected orbit, nu and nud the first two derivatives of par's
+ * spin phase at te0 (glitches active there and waves included), computed with tau_B0 once per call. x_i is the folded
+ * phase of t_i under par at the emission time (crimp_calcphase with CRIMP_PART_EMISSION). delta_i equals Phi(t_i; par)
+ * - Phi(t_i; full(p)) up to the dropped |phi_par'''| |dtau|^3 / 6; a photon with a glitch epoch of par between te0 and
+ * teF is outside the contract. With no BINARY slot, or every orbital entry 0, R is exactly 0.
+ * A vector whose corrected orbit is outside the limits of crimp_binary_delay (a non-finite field included) is
+ * inadmissible: NLL = +inf, its delta row +inf, no solve is run for it and the sampler rejects it as it rejects a
+ * proposal outside the box. A photon whose delay iteration reaches its cap makes the NLL +inf.
+ * CRIMP_ERR_ARG of both calls, nothing written: the texts of crimp_photon_nll / _mcmc but "binary models are not
+ * fitted yet"; "the model has no binary"; a base orbit outside the limits (the texts of crimp_binary_delay); "slot
+ * names an orbit field outside CRIMP_ORBIT_PB..CRIMP_ORBIT_A1DOT"; "two slots name one orbit field"; "slot names an
+ * orbit field the model's kind does not have" (ECC, OM, OMDOT, GAMMA under ELL1; EPS1, EPS2 under BT).
+ * CRIMP_FLAG_TIME_KERNELS times the kernel of the per-photon constants with the others. */
+
+/* crimp_photon_nll under an orbit: the same arrays, outputs and independence of P and the launch shape. */
+int crimp_photon_orbit_nll(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                           const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                           const double* pvec, int64_t P, double* nll, double* delta, uint32_t flags, void* stream);
+
+/* crimp_photon_mcmc under an orbit: the same move, halves, box prior, Philox counters and outputs; logprob equals
+ * -crimp_photon_orbit_nll(chain) bit for bit, and no inadmissible vector enters a chain. */
+int crimp_photon_orbit_mcmc(const double* t_mjd, const double* x, int64_t n, const crimp_timing_model* par,
+                            const crimp_fit_map* map, const crimp_template* tpl, double norm, int32_t phoff,
+                            const double* p0, const double* lo, const double* hi, int32_t W, int64_t steps,
+                            uint64_t seed, double* chain, double* logprob, int64_t* accepted, uint32_t flags,
+                            void* stream);
 
 /* Interval selection of measureToAs (measureToAs.py:168-182): TIME[(TIME >= start) & (TIME <= end)] per ToA interval
  * (:173-174) and its first / last photon (ToA_mid, :182).
